@@ -50,7 +50,16 @@ def parse():
                     help="arithmetic of the headline frame (default fp32, the reference's; the "
                          "fp16 frame is reported as the `fp16` leg)")
     ap.add_argument("--tile-rows", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="default scene: after the headline also measure everything else -- the "
+                         "executed-evaluation count of the roofline, hit fraction, the fp32-split / "
+                         "fp16 / mixed / scan-free legs, api_paths, the train legs and the CPU "
+                         "baseline with its accuracy figures (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the arrays the last timed step returned as "
+                         "DIR/<name>.npy (float32); default scene and --scene colocate|dtu|nerfle")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full (or --scene train|path): skip the CPU baseline")
     ap.add_argument("--cpu-crop", type=int, default=128, help="side of the CPU-baseline crop")
     ap.add_argument("--no-fp32-check", action="store_true", help="no-op (kept for tools/)")
     ap.add_argument("--no-extra-legs", action="store_true",
@@ -230,10 +239,30 @@ def _copy_to_oracle(dst, src):
 
 
 LIGHT_GAIN = 10.0  # bench frame light magnitude x10: RGB spans most of [0, 1] (build_scene)
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes written at most, over all arrays
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: write each array the last timed step returned as DIR/<name>.npy (float32).
+    Arrays that together pass DUMP_BUDGET are cut to a fixed, seeded sample of their flattened
+    elements (the same indices every run, in ascending order), each in proportion to its size."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in arrays.items()}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = max(1, int(v.numel() * (DUMP_BUDGET - 4096 * len(arrays)) / total))
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(v.numel(), generator=g)[:keep].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), v.numpy())
 
 
 def main():
     args = parse()
+    if args.dump_outputs and args.scene in ("train", "path"):
+        raise SystemExit(f"--dump-outputs is not implemented for --scene {args.scene}")
     if args.scene == "train":
         return bench_train(args)
     if args.scene == "path":
@@ -286,17 +315,22 @@ def main():
         _lib.profile_enable(True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        frames = None
         for _ in range(args.steps):
-            step()
+            frames = step()
         torch.cuda.synchronize()
         if dist_on:
             torch.distributed.barrier()
         elapsed = time.perf_counter() - t0
         _lib.profile_enable(False)
+        if args.dump_outputs and rank == 0 and frames is not None:
+            # the step's return value: the assembled RGBA frames [views, size, size, 4]
+            dump_outputs(args.dump_outputs, {"frames": frames})
         march_kernel = MARCH_KERNEL[args.precision]
         k_ms, k_n = _lib.profile_read(march_kernel)
         i_ms, i_n = _lib.profile_read("k_intersect")
-        evals = count_evals(step)
+        # the executed-evaluation count takes one more render: --full only
+        evals = count_evals(step) if args.full else None
         elapsed = max_over_ranks(elapsed, world, device, force=dist_on)
 
     ms_step = 1000 * elapsed / args.steps
@@ -308,7 +342,7 @@ def main():
     roof["intersect_ms"] = i_ms / max(i_n, 1)
 
     extra = {}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         with torch.no_grad():
             hit_frac = float(rr_hit_fraction(rr))
         extra["hit_fraction"] = round(hit_frac, 4)
@@ -379,8 +413,11 @@ def march_roofline(kernel, precision, rays, samples, k_ms, k_n, evals, size):
     avg_kernel_ms = k_ms / max(k_n, 1)
     achieved = flop_launch / (avg_kernel_ms * 1e-3) / 1e12
     peak = PEAK_TFLOPS[precision]
-    exec_flop = (evals - rays) * FLOP_SDF_8x256 * products
-    exec_achieved = exec_flop / (avg_kernel_ms * 1e-3) / 1e12
+    if evals is None:  # not counted in this run (a plain run of the headline)
+        exec_flop = exec_achieved = None
+    else:
+        exec_flop = (evals - rays) * FLOP_SDF_8x256 * products
+        exec_achieved = exec_flop / (avg_kernel_ms * 1e-3) / 1e12
     traffic, source = None, None
     pmc_path = os.path.join(ROOT, "profiles", f"pmc_{kernel}.json")
     if os.path.exists(pmc_path):
@@ -399,7 +436,7 @@ def march_roofline(kernel, precision, rays, samples, k_ms, k_n, evals, size):
         "flop_basis": "algorithmic: every ray at every march step and scan point "
                       "(sdfs.py:119-131, 232-249)",
         "executed_flop_per_launch": exec_flop, "executed_achieved": exec_achieved,
-        "executed_frac": exec_achieved / peak, "avg_kernel_ms": avg_kernel_ms, "launches": k_n,
+        "executed_frac": None if evals is None else exec_achieved / peak, "avg_kernel_ms": avg_kernel_ms, "launches": k_n,
     }
     if split:
         out["flop_basis"] = ("MFMA work issued: 3 f16 products per f32 product (hi*hi, hi*lo, "
@@ -869,13 +906,16 @@ def bench_other(args):
         _lib.profile_enable(True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        frames = None
         for _ in range(args.steps):
-            step()
+            frames = step()
         torch.cuda.synchronize()
         if dist_on:
             torch.distributed.barrier()
         elapsed = time.perf_counter() - t0
         _lib.profile_enable(False)
+        if args.dump_outputs and rank == 0 and frames is not None:
+            dump_outputs(args.dump_outputs, {"frames": frames})
         k_ms, k_n = _lib.profile_read(kernel)
         evals = count_evals(render) if sc["kind"] == "march" else None
         elapsed = max_over_ranks(elapsed, world, device, force=dist_on)

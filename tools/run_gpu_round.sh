@@ -13,8 +13,9 @@ if [ "$STEP" = all ] || [ "$STEP" = tests ]; then
   rc=$?; echo "SMOKE EXIT $rc"; tail -2 gpurun_out/smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "$STEP" = all ] || [ "$STEP" = bench ]; then
-  timeout -k 10 600 python -u bench.py > gpurun_out/bench.log 2>&1
-  rc=$?; echo "BENCH EXIT $rc"; tail -1 gpurun_out/bench.log; [ $rc -eq 0 ] || exit $rc
+  # the whole line (legs, train, CPU baseline): --full; BENCH_LOG names the log (default bench.log)
+  timeout -k 10 600 python -u bench.py --full > "${BENCH_LOG:=bench.log}" 2>&1
+  rc=$?; echo "BENCH EXIT $rc"; tail -1 "$BENCH_LOG"; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "$STEP" = all ] || [ "$STEP" = prof ]; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-fp32-check --no-extra-legs > gpurun_out/prof.log 2>&1
