@@ -175,6 +175,25 @@ int nrt_sdf_create_sphere_blob(int32_t n, const float* host_centers, const float
  * after an optimiser step, with no host round trip.  NRT_EINVAL for other SDF kinds. */
 int nrt_sdf_refresh_spheres(nrt_sdf* sdf, const float* device_centers, const float* device_radii,
                             const float* device_tfs, void* stream);
+/* RoundBoxSDF (sdfs.py:46-68; replaces its forward's torch ops): smooth_min_k over
+ * sd_i = |max(q, 1e-7)| + min(max(q_x, q_y, q_z), -1e-7) with q = |(I+tfs_i) p - c_i| - b_i.
+ * host_centers [n,3], host_b [n,3], host_tfs [n,3,3]; the module's radii are never read by the
+ * reference's forward and are not an argument.  1 <= n <= 1024.  No MLP: FP32 at every precision. */
+int nrt_sdf_create_round_boxes(int32_t n, const float* host_centers, const float* host_b,
+                               const float* host_tfs, float k, nrt_sdf** out);
+/* CapsuleSDF (sdfs.py:70-86; replaces its forward's torch ops): smooth_min_k over
+ * sd_i = |pa - ba h| - r_i with pa = p - a_i, ba = b_i - a_i, h = (pa . ba) / clamp(ba . ba, 0, 1)
+ * (the clamp binds to the denominator, h is unclamped: infinite cylinders, as the reference).
+ * host_a [n,3], host_b [n,3], host_radii [n].  1 <= n <= 1024. */
+int nrt_sdf_create_capsules(int32_t n, const float* host_a, const float* host_b,
+                            const float* host_radii, float k, nrt_sdf** out);
+/* Rewrite the primitive table of a round-box / capsule SDF from device tensors (same layouts as
+ * the host arguments of its create call, same n), stream-ordered, like nrt_sdf_refresh_spheres.
+ * NRT_EINVAL for other SDF kinds. */
+int nrt_sdf_refresh_round_boxes(nrt_sdf* sdf, const float* device_centers, const float* device_b,
+                                const float* device_tfs, void* stream);
+int nrt_sdf_refresh_capsules(nrt_sdf* sdf, const float* device_a, const float* device_b,
+                             const float* device_radii, void* stream);
 int nrt_sdf_destroy(nrt_sdf* sdf);
 
 /* out[M] = sdf(p[M,3]) */
@@ -202,6 +221,29 @@ int nrt_sphere_smoothmin_backward(const float* p, int64_t P, const float* center
                                   const float* radii, const float* tfs, int32_t n, float k,
                                   const float* dvalue, const float* dgrad, float* dcenters,
                                   float* dradii, float* dtfs, void* workspace, void* stream);
+
+/* RoundBoxSDF's / CapsuleSDF's smooth-min for training (sdfs.py:61-68, 78-86, utils.py:386-387;
+ * replaces the torch ops of their forward and of SDF.autograd_diff's create_graph=True gradient,
+ * sdfs.py:184-197, when the points carry no gradient): value[P] and grad[P,3] = d value / d p
+ * (either output may be NULL).  kind selects the primitive and the meaning of the three device
+ * tensors:  NRT_PRIM_ROUND_BOX  A = centers [n,3], B = b [n,3], C = tfs [n,3,3]
+ *           NRT_PRIM_CAPSULE    A = a [n,3],       B = b [n,3], C = radii [n]
+ * 1 <= n <= 1024. */
+#define NRT_PRIM_ROUND_BOX 3
+#define NRT_PRIM_CAPSULE 4
+int nrt_prim_smoothmin_forward(int32_t kind, const float* p, int64_t P, const float* A,
+                               const float* B, const float* C, int32_t n, float k, float* value,
+                               float* grad, void* stream);
+/* The backward of both outputs with respect to the primitive parameters (for grad: the double
+ * backward of the normal): dA, dB, dC (shapes of A, B, C; each may be NULL) are overwritten with
+ * sum_points dvalue . d value / d theta + dgrad . d grad / d theta; dvalue [P] and dgrad [P,3] may
+ * be NULL (no gradient).  Deterministic (fixed-order sums: point slices, then a reduce kernel).
+ * workspace: nrt_prim_smoothmin_workspace_bytes(P) bytes. */
+size_t nrt_prim_smoothmin_workspace_bytes(int64_t P);
+int nrt_prim_smoothmin_backward(int32_t kind, const float* p, int64_t P, const float* A,
+                                const float* B, const float* C, int32_t n, float k,
+                                const float* dvalue, const float* dgrad, float* dA, float* dB,
+                                float* dC, void* workspace, void* stream);
 
 typedef struct {
   int32_t max_steps;   /* SDF.max_steps (sdfs.py:96; scripts set 32/64/256)               */
@@ -581,6 +623,13 @@ int nrt_profile_flop(const char* name, double* flop);
  *                      k_march3) stage each wave's finished packed t and whole-scan keys in LDS
  *                      per 16-ray line and write whole lines (fewer, coalesced write requests);
  *                      0: one 4- / 8-byte store per ray; the same words either way
+ *   "prim_march"     1  round-box / capsule SDFs (no MLP) evaluate, march, take normals and shadow
+ *                      rays on the lane-per-ray kernels k_prim_eval / k_prim_intersect /
+ *                      k_prim_normals / k_prim_occlusion (64 rays a wave, no LDS slab), the
+ *                      table read through the constant cache; 2: the same kernels reading an LDS
+ *                      copy of the table staged once per block; 0: the per-wave kernels (32 rays
+ *                      a wave) on the same device functions.  The same bits for every value (a
+ *                      ray's values do not depend on the schedule)
  * nrt_set_option returns NRT_EINVAL for an unknown name or a negative value.
  * ------------------------------------------------------------------------------------- */
 int nrt_set_option(const char* name, int64_t value);

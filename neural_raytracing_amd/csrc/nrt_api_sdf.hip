@@ -109,6 +109,7 @@ int nrt_sdf_eval(const nrt_sdf* s, const float* p, int64_t M, float* out, int pr
   if (!s || M < 0) { set_error("nrt_sdf_eval: bad argument"); return NRT_EINVAL; }
   if (M == 0) return NRT_OK;
   if (!p || !out) { set_error("nrt_sdf_eval: null p / out"); return NRT_EINVAL; }
+  if (prim_lanes(s)) return prim_eval(s, p, M, out, (hipStream_t)stream);
   if ((precision == NRT_FP32_SPLIT || precision == NRT_MIXED) && ring3_supported(s) &&
       option(OPT_RING32) != 0)
     return ring_eval3(s, p, M, out, (hipStream_t)stream);
@@ -154,6 +155,8 @@ static size_t grad_workspace_bytes(const nrt_sdf* s) {
 static int launch_grad(const nrt_sdf* s, const float* p, const int32_t* index, const int32_t* count,
                        int64_t M, float* grad, float* n_out, float* p_io, float eps, void* ws,
                        hipStream_t st) {
+  // round boxes / capsules: one point per lane (k_prim_normals)
+  if (prim_lanes(s)) return prim_normals(s, p, index, count, M, grad, n_out, p_io, eps, st);
   LdsPlan lp = grad_plan(s);
   const int64_t waves_needed = ceil_div64(M, 32);
   int blocks = (int)std::min<int64_t>(kGradBlocks, ceil_div64(waves_needed, lp.waves));
@@ -269,6 +272,10 @@ int nrt_sdf_intersect(const nrt_sdf* s, const float* rays, int64_t P, const nrt_
       k_keys_index<><<<dim3(ceil_div64(P, 256)), dim3(256), 0, st>>>(keys, P, ma.scan_idx);
       rc0 = check_launch("k_keys_index");
     }
+  } else if (prim_lanes(s)) {
+    // round boxes / capsules: one ray per lane (k_prim_intersect), FP32 at every precision
+    ProfScope prof("k_intersect", st);
+    rc0 = prim_intersect(s, rays, P, ma, t, hit, p, n, raw_n, throughput, idx, cnt, st);
   } else {
     ProfScope prof("k_intersect", st);
     NRT_NB_SWITCH(s->host_dev.nb, {
@@ -334,6 +341,11 @@ int launch_occlusion(const nrt_sdf* s, const float* rays, int64_t P, const int32
       return split ? ring3_launch(s, rays, P, ma, nullptr, nullptr, nullptr, st, 4, visible)
                    : ring_occlusion32(s, rays, P, ma, visible, st);
     }
+  }
+  if (prim_lanes(s)) {
+    ProfScope prof("k_occlusion", st);
+    return prim_occlusion(s, rays, P, count, max_t, max_steps, eps, visible,
+                          profile_eval_counter(), st);
   }
   int hidden, ke;
   sdf_dims(s, hidden, ke);

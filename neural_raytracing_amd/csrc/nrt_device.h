@@ -144,10 +144,12 @@ struct RProgDev {
 };
 
 struct SdfDev {
-  int kind;         // 0 unit sphere, 1 MLP, 2 sphere blob (+ optional shift MLP)
-  int n_spheres;
-  float k;          // smooth-min sharpness (32)
-  const float* spheres;  // [n][16]: (I+tfs) row-major (9), centre (3), radius (1), pad (3)
+  int kind;         // 0 unit sphere, 1 MLP, 2 sphere blob (+ optional shift MLP),
+                    // 3 round boxes, 4 capsules (no MLP; nrt_prim.h)
+  int n_spheres;    // primitives of the table
+  float k;          // smooth-min sharpness (32; 16 for kinds 3 and 4)
+  const float* spheres;  // [n][16]: (I+tfs) row-major (9), centre (3), radius (1), pad (3);
+                         // kinds 3 and 4: the layouts of nrt_prim.h
   const MlpDev* mlp;     // MLP or shift MLP (nullptr if none)
   int nb;
 };

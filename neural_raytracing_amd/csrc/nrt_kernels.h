@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "nrt_internal.h"
+#include "nrt_prim.h"
 #include "nrt_ring3.h"
 
 namespace nrt {
@@ -109,11 +110,27 @@ __device__ __forceinline__ void spheres_grad(const SdfDev& s, float x, float y, 
   g[0] = gx * sc; g[1] = gy * sc; g[2] = gz * sc;
 }
 
+// RoundBoxSDF / CapsuleSDF (SdfDev kinds 3 and 4, sdfs.py:46-86; expressions in nrt_prim.h): FP32
+// at every precision (no MLP to lower, no fast exp), the table through the constant address space
+// like spheres_value
+__device__ __forceinline__ float prim_value(const SdfDev& s, float x, float y, float z) {
+  const ConstF* tab = (const ConstF*)s.spheres;
+  return s.kind == prim::kBox ? prim::table_value<prim::kBox>(tab, s.n_spheres, s.k, x, y, z)
+                              : prim::table_value<prim::kCapsule>(tab, s.n_spheres, s.k, x, y, z);
+}
+
+__device__ __forceinline__ void prim_grad(const SdfDev& s, float x, float y, float z, float g[3]) {
+  const ConstF* tab = (const ConstF*)s.spheres;
+  if (s.kind == prim::kBox) prim::table_grad<prim::kBox>(tab, s.n_spheres, s.k, x, y, z, g);
+  else prim::table_grad<prim::kCapsule>(tab, s.n_spheres, s.k, x, y, z, g);
+}
+
 // SDF value of this lane's point; every lane of the wave must call it (MFMA is wave-wide).
 template <bool F16, int NB>
 __device__ __forceinline__ float sdf_value(const SdfDev& s, float x, float y, float z,
                                            const WaveLds& l, int RS, float* zs) {
   if (s.kind == 0) return sqrtf(x * x + y * y + z * z) - 1.f;
+  if (s.kind >= prim::kBox) return prim_value(s, x, y, z);
   float v = 0.f;
   if (s.kind == 2) v = spheres_value<F16>(s, x, y, z);
   if (s.mlp) {
@@ -138,6 +155,7 @@ __device__ __forceinline__ void sdf_gradient(const SdfDev& s, float x, float y, 
     if (n > 0.f) { g[0] = x / n; g[1] = y / n; g[2] = z / n; }
     return;
   }
+  if (s.kind >= prim::kBox) { prim_grad(s, x, y, z, g); return; }
   if (s.kind == 2) spheres_grad(s, x, y, z, g);
   if (s.mlp) {
     EncIn e;

@@ -39,6 +39,7 @@ enum Option {
   OPT_TRAIN_SAVE,      // "train_save"
   OPT_WGRAD_TILE,      // "wgrad_tile"
   OPT_MARCH_STAGE,     // "march_stage"
+  OPT_PRIM_MARCH,      // "prim_march"
   OPT_COUNT
 };
 int64_t option(Option o);
@@ -260,6 +261,25 @@ int ring_normals(const nrt_sdf* s, const int32_t* idx, const int32_t* cnt, int64
 int launch_occlusion(const nrt_sdf* s, const float* rays, int64_t P, const int32_t* count,
                      const float* max_t, int32_t max_steps, float eps, uint8_t* visible,
                      int precision, hipStream_t st);
+
+// ---- RoundBoxSDF / CapsuleSDF (SdfDev kinds 3 and 4, nrt_prim.hip) ----
+// Lane-per-ray kernels for the MLP-free primitive sets (64 rays a wave, no per-wave LDS slab),
+// the same contracts as k_sdf_eval / k_intersect / k_sdf_grad / k_occlusion.  Option
+// "prim_march": 1 reads the table through the constant cache, 2 from an LDS copy staged once per
+// block, 0 leaves these kinds on the per-wave kernels (the same device functions: same bits).
+inline bool prim_kind(const nrt_sdf* s) { return s->host_dev.kind >= prim::kBox; }
+inline bool prim_lanes(const nrt_sdf* s) { return prim_kind(s) && option(OPT_PRIM_MARCH) != 0; }
+int prim_eval(const nrt_sdf* s, const float* p, int64_t M, float* out, hipStream_t st);
+int prim_intersect(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma, float* t,
+                   uint8_t* hit, float* p, float* n, float* raw_n, float* thr, int32_t* idx,
+                   int32_t* cnt, hipStream_t st);
+// raw gradient at p[index[i]] (i < *count, or i < M without a list): grad, then the unit normal
+// and p_io += 5 eps n when n_out / p_io are given (k_sdf_grad's contract)
+int prim_normals(const nrt_sdf* s, const float* p, const int32_t* index, const int32_t* count,
+                 int64_t M, float* grad, float* n_out, float* p_io, float eps, hipStream_t st);
+int prim_occlusion(const nrt_sdf* s, const float* rays, int64_t P, const int32_t* count,
+                   const float* max_t, int32_t max_steps, float eps, uint8_t* visible,
+                   unsigned long long* evals, hipStream_t st);
 
 // ---- shading programs (nrt_prog.hip) ----
 int build_program(const std::vector<const nrt_mlp*>& mlps, nrt_prog& out);

@@ -192,6 +192,105 @@ def sphere_part(sdf, p):
     return (-(-32. * sd).exp().sum(dim=0).clamp(min=1e-4).log() / 32.).reshape(p.shape[:-1])
 
 
+# ---- RoundBoxSDF / CapsuleSDF (sdfs.py:46-86): smooth-min of n primitives, no residual MLP ------
+
+PRIM_SMOOTHMIN_K = 16.0  # sdfs.py:68, 86
+# nrt_sdf_create_round_boxes / _capsules and nrt_prim_smoothmin_* take at most 1024 primitives:
+# larger modules march on the callable path and train on the torch restatements below
+PRIM_MAX = 1024
+PRIM_ROUND_BOX, PRIM_CAPSULE = 3, 4  # include/nrt.h NRT_PRIM_*
+
+
+def round_box_part(sdf, p):
+    """RoundBoxSDF.forward (sdfs.py:61-68) in torch, in the reference's op order: the CPU path,
+    points that carry gradients (a warp around the SDF) and tables over PRIM_MAX.  ``radii`` is
+    never read, as in the reference."""
+    flat = p.reshape(-1, 3).unsqueeze(0)
+    tfs = sdf.tfs + torch.eye(3, device=p.device, dtype=sdf.tfs.dtype).unsqueeze(0)
+    q = (torch.einsum("ijk,ibk->ibj", tfs, flat.expand(tfs.shape[0], -1, -1)) -
+         sdf.centers.unsqueeze(1)).abs() - sdf.b.unsqueeze(1)
+    up = q.clamp(min=1e-7).norm(p=2, dim=-1, keepdim=True)
+    x, y, z = q.split(1, dim=-1)
+    down = torch.maximum(x, torch.maximum(y, z)).clamp(max=-1e-7)
+    sd = up + down
+    k = PRIM_SMOOTHMIN_K
+    return (-(-k * sd).exp().sum(dim=0).clamp(min=1e-4).log() / k).reshape(p.shape[:-1])
+
+
+def capsule_part(sdf, p):
+    """CapsuleSDF.forward (sdfs.py:78-86) in torch: the clamp binds to the denominator, so h is
+    unclamped (infinite cylinders), as the reference."""
+    pa = p.reshape(-1, 3).unsqueeze(0) - sdf.a.unsqueeze(1)
+    ba = (sdf.b - sdf.a).unsqueeze(1)
+    h = (pa * ba).sum(dim=-1, keepdim=True) / \
+        (ba * ba).sum(dim=-1, keepdim=True).clamp(min=0, max=1)
+    sd = (pa - ba * h).norm(p=2, dim=-1) - sdf.radii.unsqueeze(-1)
+    k = PRIM_SMOOTHMIN_K
+    return (-(-k * sd).exp().sum(dim=0).clamp(min=1e-4).log() / k).reshape(p.shape[:-1])
+
+
+def prim_kind(sdf):
+    """(NRT_PRIM_* kind, the three parameter tensors in the C ABI's order, torch restatement) of a
+    RoundBoxSDF / CapsuleSDF, or None."""
+    from .shapes.sdfs import CapsuleSDF, RoundBoxSDF
+    if isinstance(sdf, RoundBoxSDF):
+        return PRIM_ROUND_BOX, (sdf.centers, sdf.b, sdf.tfs), round_box_part
+    if isinstance(sdf, CapsuleSDF):
+        return PRIM_CAPSULE, (sdf.a, sdf.b, sdf.radii), capsule_part
+    return None
+
+
+class _PrimSmoothMinFn(torch.autograd.Function):
+    """(value, d value / d p) of RoundBoxSDF's / CapsuleSDF's smooth-min on
+    nrt_prim_smoothmin_forward, with the primitive parameters' gradients of both outputs from
+    nrt_prim_smoothmin_backward (for the gradient output: the double backward of the
+    create_graph=True normal, sdfs.py:184-197).  kind: PRIM_ROUND_BOX (A, B, C = centers, b, tfs)
+    or PRIM_CAPSULE (a, b, radii).  The points carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, p, kind, A, B, C):
+        P, n = p.shape[0], A.shape[0]
+        value = torch.empty(P, device=p.device)
+        grad = torch.empty(P, 3, device=p.device)
+        a, b, c = (x.detach().float().contiguous() for x in (A, B, C))
+        _lib.call("nrt_prim_smoothmin_forward", kind, _lib.ptr(p), P, _lib.ptr(a), _lib.ptr(b),
+                  _lib.ptr(c), n, PRIM_SMOOTHMIN_K, _lib.ptr(value), _lib.ptr(grad), _lib.stream())
+        ctx.save_for_backward(p, a, b, c)
+        ctx.kind = kind
+        return value, grad
+
+    @staticmethod
+    def backward(ctx, dvalue, dgrad):
+        if torch.is_grad_enabled():
+            raise _lib.NrtError("third derivatives of the RoundBoxSDF / CapsuleSDF smooth-min are "
+                                "not on the HIP path")
+        p, a, b, c = ctx.saved_tensors
+        P, n = p.shape[0], a.shape[0]
+        lib = _lib.load(require_device=True)
+        da = torch.empty_like(a) if ctx.needs_input_grad[2] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[3] else None
+        dc = torch.empty_like(c) if ctx.needs_input_grad[4] else None
+        dv = None if dvalue is None else dvalue.float().contiguous()
+        dg = None if dgrad is None else dgrad.float().contiguous()
+        ws = torch.empty(lib.nrt_prim_smoothmin_workspace_bytes(P), dtype=torch.uint8,
+                         device=p.device)
+        _lib.call("nrt_prim_smoothmin_backward", ctx.kind, _lib.ptr(p), P, _lib.ptr(a), _lib.ptr(b),
+                  _lib.ptr(c), n, PRIM_SMOOTHMIN_K, _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(da),
+                  _lib.ptr(db), _lib.ptr(dc), _lib.ptr(ws), _lib.stream())
+        return None, None, da, db, dc
+
+
+def _fused_prim(tensors, p):
+    return p.is_cuda and all(t.is_cuda for t in tensors) and tensors[0].shape[0] <= PRIM_MAX
+
+
+def prim_smoothmin(kind, tensors, p):
+    """(value, gradient) at points p [..., 3] that carry no gradient, on the fused kernels."""
+    flat = p.detach().reshape(-1, 3).float().contiguous()
+    v, g = _PrimSmoothMinFn.apply(flat, kind, *tensors)
+    return v.reshape(p.shape[:-1]), g.reshape(p.shape)
+
+
 def sdf_value(sdf, p):
     """sdf(p) with gradients for the SDF's parameters."""
     from .neural_blocks import SkipConnMLP
@@ -202,6 +301,12 @@ def sdf_value(sdf, p):
         return torch.norm(p, dim=-1) - 1
     if isinstance(sdf, SkipConnMLP):
         return sdf(p).reshape(p.shape[:-1])
+    pk = prim_kind(sdf)
+    if pk is not None:
+        kind, tensors, part = pk
+        if _fused_prim(tensors, p) and not p.requires_grad:
+            return prim_smoothmin(kind, tensors, p)[0]  # fused forward + parameter backward
+        return part(sdf, p)  # points with a gradient, CPU tensors, tables over the limit
     if _is_sphere_sdf(sdf):
         if _fused_smoothmin(sdf, p) and not p.requires_grad:
             out = sphere_smoothmin(sdf, p)[0]  # fused forward + parameter backward
@@ -224,6 +329,16 @@ def sdf_gradient(sdf, p):
         return p / torch.norm(p, dim=-1, keepdim=True)
     if isinstance(sdf, SkipConnMLP):
         return input_gradient(sdf, p)
+    pk = prim_kind(sdf)
+    if pk is not None:
+        kind, tensors, part = pk
+        if _fused_prim(tensors, p):
+            return prim_smoothmin(kind, tensors, p)[1]  # fused gradient + its double backward
+        with torch.enable_grad():
+            q = p.clone().requires_grad_(True)
+            out = part(sdf, q)
+            (g,) = torch.autograd.grad(out, q, torch.ones_like(out), create_graph=True)
+        return g
     if _is_sphere_sdf(sdf):
         if _fused_smoothmin(sdf, p):
             g = sphere_smoothmin(sdf, p)[1]  # fused gradient + its double backward

@@ -1,8 +1,9 @@
 """SDF shapes (shapes/sdfs.py): the sphere-tracing march, the 128-step coarse scan and the
-normals run in ``nrt_sdf_intersect``; ``SphereSDF`` / ``SkipConnMLP`` SDFs evaluate in
-``nrt_sdf_eval``.  Any other SDF callable (a warp or displacement around a packed SDF,
-edit_dtu.py:86-100) is evaluated by the caller between the HIP march / scan / shadow steps
-(``nrt_*_callable_step``), with autograd normals through the callable as sdfs.py:184-197."""
+normals run in ``nrt_sdf_intersect``; ``SphereSDF`` / ``SkipConnMLP`` / ``RoundBoxSDF`` /
+``CapsuleSDF`` SDFs evaluate in ``nrt_sdf_eval``.  Any other SDF callable (a warp or
+displacement around a packed SDF, edit_dtu.py:86-100) is evaluated by the caller between the
+HIP march / scan / shadow steps (``nrt_*_callable_step``), with autograd normals through the
+callable as sdfs.py:184-197."""
 import ctypes
 import random
 
@@ -13,7 +14,9 @@ import torch.nn.functional as F
 from ... import _lib
 from .._handles import _Handle, _cache, _host, mlp_handle, train_handle
 from ..interaction import MixedInteraction
-from ..differentiable import coordinate_system, needs_grad, sdf_gradient, sdf_value
+from ..differentiable import (PRIM_MAX, PRIM_ROUND_BOX, PRIM_SMOOTHMIN_K, capsule_part,
+                              coordinate_system, needs_grad, prim_kind, round_box_part,
+                              sdf_gradient, sdf_value)
 from ..neural_blocks import SkipConnMLP
 
 
@@ -84,9 +87,30 @@ def sdf_handle(sdf):
                 mh.value if mh is not None else None, ctypes.byref(out)), "nrt_sdf_create_sphere_blob")
             return _Handle(out, "nrt_sdf_destroy", [mh] if mh is not None else [])
         return _cache(sdf, params, build).value
+    pk = prim_kind(sdf)
+    if pk is not None:
+        kind, tensors, _ = pk
+        _check_prim_count(sdf, tensors)
+        return _cache(sdf, list(tensors), lambda: _create_prims(kind, tensors)).value
     raise _lib.NrtError(f"SDF callable {getattr(sdf, '__name__', type(sdf).__name__)} has no HIP "
-                        "implementation (supported: SPHERE_SDF, SphereSDF, SkipConnMLP and their "
-                        "TorchScript modules)")
+                        "implementation (supported: SPHERE_SDF, SphereSDF, RoundBoxSDF, CapsuleSDF, "
+                        "SkipConnMLP, and the TorchScript modules of SphereSDF and SkipConnMLP)")
+
+
+def _check_prim_count(sdf, tensors):
+    if tensors[0].shape[0] > PRIM_MAX:
+        raise _lib.NrtError(f"{type(sdf).__name__} with {tensors[0].shape[0]} primitives is not a "
+                            f"HIP SDF kind (at most {PRIM_MAX}): it marches as a callable")
+
+
+def _create_prims(kind, tensors):
+    """nrt_sdf_create_round_boxes / _capsules from host copies of the module's tensors."""
+    a, b, c = (_host(t) for t in tensors)
+    name = "nrt_sdf_create_round_boxes" if kind == PRIM_ROUND_BOX else "nrt_sdf_create_capsules"
+    out = ctypes.c_void_p()
+    _lib.check(getattr(_lib.load(), name)(a.shape[0], a.data_ptr(), b.data_ptr(), c.data_ptr(),
+                                          PRIM_SMOOTHMIN_K, ctypes.byref(out)), name)
+    return _Handle(out, "nrt_sdf_destroy")
 
 
 def train_sdf_handle(sdf):
@@ -128,6 +152,27 @@ def train_sdf_handle(sdf):
                       _lib.ptr(s.radii.detach()), _lib.ptr(s.tfs.detach()), _lib.stream())
             cached[3] = vers
         return cached[1].value
+    pk = prim_kind(s)
+    if pk is not None:
+        # the primitive table is built once, then rewritten on the device
+        # (nrt_sdf_refresh_round_boxes / _capsules) when an optimiser step changed its tensors
+        kind, tensors, _ = pk
+        _check_prim_count(s, tensors)
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            return sdf_handle(sdf)
+        shapes = tuple((t.data_ptr(), tuple(t.shape)) for t in tensors)
+        vers = tuple(t._version for t in tensors)
+        cached = getattr(s, "_nrt_train_sdf", None)
+        if cached is None or cached[1] != shapes:
+            cached = [_create_prims(kind, tensors), shapes, vers]
+            object.__setattr__(s, "_nrt_train_sdf", cached)
+        elif cached[2] != vers:
+            name = ("nrt_sdf_refresh_round_boxes" if kind == PRIM_ROUND_BOX
+                    else "nrt_sdf_refresh_capsules")
+            _lib.call(name, cached[0].value, *(_lib.ptr(t.detach()) for t in tensors),
+                      _lib.stream())
+            cached[2] = vers
+        return cached[0].value
     return sdf_handle(sdf)
 
 
@@ -139,13 +184,17 @@ def march_handle(sdf):
 
 def is_hip_sdf(sdf):
     """True for the SDFs nrt_sdf packs (SPHERE_SDF, SphereSDF, SkipConnMLP and their TorchScript
-    modules); anything else is a callable the march evaluates between its HIP steps."""
+    modules; RoundBoxSDF and CapsuleSDF of at most PRIM_MAX primitives); anything else is a
+    callable the march evaluates between its HIP steps."""
     from ..script_modules import resolve
     try:
         s = resolve(sdf)
     except _lib.NrtError:
         return False
-    return s is SPHERE_SDF or isinstance(s, SkipConnMLP) or _is_sphere_sdf(s)
+    if s is SPHERE_SDF or isinstance(s, SkipConnMLP) or _is_sphere_sdf(s):
+        return True
+    pk = prim_kind(s)
+    return pk is not None and pk[1][0].shape[0] <= PRIM_MAX
 
 
 def _looks_like_sphere_sdf(m):
@@ -491,10 +540,23 @@ class SDF:
         return g.reshape(p.shape)
 
 
+def _prim_forward(sdf, p, part):
+    """forward of RoundBoxSDF / CapsuleSDF, like SphereSDF.forward: nrt_sdf_eval under no_grad,
+    sdf_value (the fused training kernels) under autograd; the torch restatement for CPU tensors
+    and for a module over the table limit (which marches as a callable through this forward)."""
+    if not p.is_cuda or not is_hip_sdf(sdf):
+        return part(sdf, p)
+    if torch.is_grad_enabled() and (p.requires_grad or needs_grad(sdf)):
+        return sdf_value(sdf, p)
+    return sdf_eval(sdf, p)
+
+
 class RoundBoxSDF(nn.Module):
-    """Rounded boxes smooth-min-ed together (sdfs.py:48-68): import-resolvable for the drivers
-    (nerf_synthetic.py:14-16, dtu.py:18-20); constructor and RNG order as the reference.  Not a
-    HIP SDF kind: SDF(sdf=RoundBoxSDF()) raises NrtError when it is marched."""
+    """Rounded boxes smooth-min-ed together (sdfs.py:46-68, k = 16, no residual MLP); constructor
+    and RNG order as the reference.  A HIP SDF kind (nrt_sdf_create_round_boxes): SDF(sdf=
+    RoundBoxSDF()) marches on the lane-per-ray kernels k_prim_* and trains on
+    nrt_prim_smoothmin_*.  ``radii`` is a parameter the reference's forward never reads: it is
+    not packed and receives no gradient."""
 
     def __init__(self, n=2 << 4, device="cuda"):
         super().__init__()
@@ -504,12 +566,13 @@ class RoundBoxSDF(nn.Module):
         self.tfs = nn.Parameter(torch.zeros(n, 3, 3, device=device, requires_grad=True))
 
     def forward(self, p):
-        raise _lib.NrtError("RoundBoxSDF has no HIP implementation (supported SDFs: SPHERE_SDF, "
-                            "SphereSDF, SkipConnMLP)")
+        return _prim_forward(self, p, round_box_part)
 
 
 class CapsuleSDF(nn.Module):
-    """Capsules smooth-min-ed together (sdfs.py:72-86): import-resolvable, like RoundBoxSDF."""
+    """Capsules smooth-min-ed together (sdfs.py:70-86, k = 16, no residual MLP): a HIP SDF kind
+    (nrt_sdf_create_capsules), like RoundBoxSDF.  As in the reference the clamp binds to the
+    denominator of h, so every primitive is an infinite cylinder."""
 
     def __init__(self, n=2 << 5, device="cuda"):
         super().__init__()
@@ -518,5 +581,4 @@ class CapsuleSDF(nn.Module):
         self.radii = nn.Parameter(0.1 * torch.rand(n, device=device, requires_grad=True) - 0.05)
 
     def forward(self, p):
-        raise _lib.NrtError("CapsuleSDF has no HIP implementation (supported SDFs: SPHERE_SDF, "
-                            "SphereSDF, SkipConnMLP)")
+        return _prim_forward(self, p, capsule_part)
