@@ -540,6 +540,11 @@ int nrt_profile_evals(uint64_t* evals);
 /* Rays the NRT_MIXED refinement re-marched on the split engine (the flagged rays, nrt_ring_mixed
  * step 2) while NRT_PROF_EVALS was enabled, since the last nrt_profile_reset.  Synchronises. */
 int nrt_profile_refined(uint64_t* rays);
+/* March launches (k_march32 / k_march3 / k_march16) that ran with line stages (nrt_kernels.h
+ * LineStage: the launch queue on, option "march_stage" on, and the stages fitting) while
+ * NRT_PROF_EVALS was enabled, since the last nrt_profile_reset.  Counted on the host where the
+ * launch is set up: nothing on the device. */
+int nrt_profile_staged(uint64_t* launches);
 /* Algorithmic FLOP of the timed launches of kernel `name` since the last nrt_profile_reset, as
  * the entries that launch it count them (the MLP backward and weight-gradient launches of the
  * training path: every multiply-add of the layers' products at their real widths, 2 FLOP each);

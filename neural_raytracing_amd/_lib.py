@@ -138,6 +138,7 @@ _SIGNATURES = {
                                 ctypes.POINTER(_I64)]),
     "nrt_profile_evals": (_I32, [ctypes.POINTER(ctypes.c_uint64)]),
     "nrt_profile_refined": (_I32, [ctypes.POINTER(ctypes.c_uint64)]),
+    "nrt_profile_staged": (_I32, [ctypes.POINTER(ctypes.c_uint64)]),
     "nrt_profile_flop": (_I32, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]),
     "nrt_set_option": (_I32, [ctypes.c_char_p, _I64]),
     "nrt_get_option": (_I32, [ctypes.c_char_p, ctypes.POINTER(_I64)]),
@@ -276,6 +277,15 @@ def profile_refined():
     while evaluation counting was enabled."""
     v = ctypes.c_uint64()
     check(load().nrt_profile_refined(ctypes.byref(v)), "nrt_profile_refined")
+    return v.value
+
+
+def profile_staged():
+    """March launches that ran with line stages (nrt_kernels.h LineStage) since the last reset
+    while evaluation counting was enabled: 0 says that a march stored every ray's words itself
+    (no launch queue, option march_stage off, or stages that would cost a resident block)."""
+    v = ctypes.c_uint64()
+    check(load().nrt_profile_staged(ctypes.byref(v)), "nrt_profile_staged")
     return v.value
 
 

@@ -68,6 +68,11 @@ ProfScope::~ProfScope() {
 }
 
 static unsigned long long* g_evals[64] = {};
+static uint64_t g_staged = 0;  // march launches with line stages (nrt_profile_staged)
+
+void profile_count_staged() {
+  if (g_prof_evals) ++g_staged;
+}
 
 unsigned long long* profile_eval_counter() {
   if (!g_prof_evals) return nullptr;
@@ -96,6 +101,7 @@ void nrt_profile_enable(int flags) {
 void nrt_profile_reset(void) {
   for (auto& r : nrt::g_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   nrt::g_recs.clear();
+  nrt::g_staged = 0;
   int dev = 0;
   if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && nrt::g_evals[dev])
     (void)hipMemset(nrt::g_evals[dev], 0, 2 * sizeof(unsigned long long));
@@ -122,6 +128,12 @@ int nrt_profile_refined(uint64_t* rays) {
   unsigned long long v = 0;
   NRT_HIP(hipMemcpy(&v, nrt::g_evals[dev] + 1, sizeof(v), hipMemcpyDeviceToHost));
   *rays = v;
+  return NRT_OK;
+}
+
+int nrt_profile_staged(uint64_t* launches) {
+  if (!launches) { set_error("nrt_profile_staged: null argument"); return NRT_EINVAL; }
+  *launches = nrt::g_staged;
   return NRT_OK;
 }
 

@@ -142,6 +142,9 @@ int max_hidden(const nrt_mlp* m);
 // device counter of executed ray-evaluations of the ring marches while profiling is enabled
 // (nullptr otherwise); read and cleared by nrt_profile_evals / nrt_profile_reset
 unsigned long long* profile_eval_counter();
+// a march is about to launch with line stages (MarchArgs::stage != 0): counted while
+// NRT_PROF_EVALS is on (nrt_profile_staged)
+void profile_count_staged();
 
 // Element order of the FP32 ring stream (MlpDev::stream32, consumed by nrt_device.h ring32 with
 // v_mfma_f32_16x16x4_f32 on 16-ray tiles).  Shared by the packer (values, nrt_pack.hip) and the

@@ -332,6 +332,10 @@ constexpr int kQueueTail = NRT_QUEUE_TAIL;    // rays per wave of the grid whose
 // ends is written with the lanes of its finished rays only.  Every ray's word is written exactly
 // once either way: the same bits as the per-ray stores.  The slot table (line, finished-ray mask)
 // lives in lanes 0 .. kStageSlots-1 of two VGPRs; all control is wave-uniform.
+// Only the packed t's stage can evict: marches differ in length, so a wave may hold rays of many
+// lines.  The key stage cannot -- every whole scan is 129 evaluations long and a wave takes a
+// line's 16 scans in order, so at most two key lines are open at once; its eviction branch is the
+// same code and is covered by the t stage's test (tests/test_gpu_line_stage.py).
 constexpr int kStageSlots = 8;
 constexpr int kStageBytes = kStageSlots * 16 * (4 + 8);  // t words, then key words
 template <class W>

@@ -33,6 +33,7 @@ int ring_march16_launch(const nrt_sdf* s, const float* rays, int64_t P, const Ma
       if (plain) {
         stage_lds(b, lds, kRingWaves);
         if (b.stage && kLdsBytes / lds != kLdsBytes / lds0) { b.stage = 0; lds = lds0; }
+        if (b.stage) profile_count_staged();
       }
       if (int rc = set_lds(kern, lds)) return rc;
       int per_cu = 0;

@@ -30,6 +30,7 @@ static int ring32_launch(const nrt_sdf* s, const float* rays, int64_t P, const M
       size_t lds = ring32::Engine<KH, KE, WV>::RING_BYTES + extra;
       MarchArgs mb = ma;
       if (plain) stage_lds(mb, lds, WV);  // the march's line stages (one block a CU)
+      if (mb.stage) profile_count_staged();
       if (int rc = set_lds(kern, lds)) return rc;
       int per_cu = 0;
       NRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * WV, lds));

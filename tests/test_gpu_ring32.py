@@ -19,7 +19,8 @@ import torch.nn.functional as F
 
 import bench
 from oracle import pathtracer_ref as R
-from tests.helpers import copy_mlp, product_mlp_like, seeded
+from tests.helpers import (assert_bit_equal, assert_outputs_written, blob, intersect_poisoned,
+                           product_mlp_like, seeded)
 from tests.report import report
 from tests.helpers import lib_opt as _lib_opt
 
@@ -43,29 +44,7 @@ def _rays(n, seed, eye=(0.0, 0.1, 1.0), spread=0.9):
 
 
 def _blob(n, hidden, freqs, act, seed=5):
-    """oracle SphereBlobSDF + the product SphereSDF with the same tensors; the shift gets a
-    visible residual (out weights x0.05) so the MLP part shapes the surface."""
-    from neural_raytracing_amd.pathtracer.neural_blocks import SkipConnMLP
-    from neural_raytracing_amd.pathtracer.shapes import SphereSDF
-    seeded(seed)
-    ref = R.SphereBlobSDF(n=n, shift_hidden=hidden, shift_freqs=freqs, shift_zero_init=False)
-    if act != "softplus":
-        ref.shift = R.SkipMLP(num_layers=8, hidden_size=hidden, out=1, freqs=freqs, activation=act)
-    with torch.no_grad():
-        ref.radii.add_(0.12)
-        ref.tfs.copy_(0.05 * torch.randn_like(ref.tfs))
-        ref.shift.out.weight.mul_(0.05)
-        ref.shift.out.bias.mul_(0.05)
-    mine = SphereSDF(n=n, device="cpu")
-    kw = {"activation": F.softplus} if act == "softplus" else {}
-    mine.shift = SkipConnMLP(num_layers=8, hidden_size=hidden, in_size=3, out=1, freqs=freqs,
-                             device="cpu", **kw)
-    with torch.no_grad():
-        mine.centers.copy_(ref.centers)
-        mine.radii.copy_(ref.radii)
-        mine.tfs.copy_(ref.tfs)
-    copy_mlp(mine.shift, ref.shift)
-    return ref, mine.cuda()
+    return blob(n, hidden, freqs, act, seed)
 
 
 def _march(sdf, rays, primary=True, steps=64, seed=12):
@@ -207,23 +186,28 @@ def test_march_line_staging_matches_per_ray_stores(prec, hidden):
     whole-scan keys through per-wave LDS line stages, nrt_kernels.h LineStage): bit-identical t,
     hit, p, n and throughput to one store per ray -- 37^2 = 1,369 rays (a ragged last line), 3
     blocks (24 waves: 384 segmented scans, the rest whole, a line split between the two), and the
-    default grid; the 128- and 256-wide shifts (the headline's width)."""
-    from neural_raytracing_amd import set_precision
+    default grid; the 128- and 256-wide shifts (the headline's width).  (The evicting case and the
+    counters that say whether a march staged at all: tests/test_gpu_line_stage.py.)"""
+    from neural_raytracing_amd import _lib
+    from neural_raytracing_amd.pathtracer.shapes.sdfs import sdf_handle
     _, mine = _blob(32, hidden, 16, "softplus", seed=21)
-    rays = _rays(37, 23, eye=(0.0, 0.2, 1.1))
-    set_precision(prec)
+    sh = sdf_handle(mine)
+    rays = _rays(37, 23, eye=(0.0, 0.2, 1.1)).reshape(-1, 6).cuda().contiguous()
     _lib_opt("march_queue", 1)
     try:
         for blocks in (3, 0):
             _lib_opt("march_blocks", blocks)
-            _lib_opt("march_stage", 0)
-            base, bh, _ = _march(mine, rays)
-            assert bh.any() and not bh.all()
-            _lib_opt("march_stage", 1)
-            it, h, _ = _march(mine, rays)
-            assert torch.equal(h, bh)
-            assert torch.equal(it.t, base.t) and torch.equal(it.throughput, base.throughput)
-            assert torch.equal(it.p, base.p) and torch.equal(it.n, base.n)
+            runs = []
+            for stage in (0, 1):
+                # every output poisoned before the launch, with guard bands: a store the stages
+                # dropped cannot find the other run's bits left in recycled memory
+                _lib_opt("march_stage", stage)
+                out, broken = intersect_poisoned(sh, rays, 64, _lib._PRECISIONS[prec])
+                assert not broken, f"march_stage={stage}: guard bands of {broken} overwritten"
+                assert_outputs_written(out, f"march_stage={stage}")
+                runs.append(out)
+            assert runs[0]["hit"].any() and not runs[0]["hit"].all()
+            assert_bit_equal(runs[1], runs[0], f"blocks={blocks}: staged vs per-ray stores")
     finally:
         _lib_opt("march_stage", 1)
 

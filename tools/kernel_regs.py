@@ -62,7 +62,9 @@ def main():
                 continue
             print(f"vgpr {k.get('vgpr_count', '?'):>4} agpr {k.get('agpr_count', '?'):>4} "
                   f"sgpr {k.get('sgpr_count', '?'):>3} lds {k.get('group_segment_fixed_size', '?'):>6} "
-                  f"scratch {k.get('private_segment_fixed_size', '?'):>5}  {name[:150]}")
+                  f"scratch {k.get('private_segment_fixed_size', '?'):>5} "
+                  f"sspill {k.get('sgpr_spill_count', '?'):>3} vspill {k.get('vgpr_spill_count', '?'):>3}"
+                  f"  {name[:150]}")
 
 
 if __name__ == "__main__":
