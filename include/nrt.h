@@ -249,7 +249,8 @@ typedef struct {
   int32_t max_steps;   /* SDF.max_steps (sdfs.py:96; scripts set 32/64/256)               */
   float epsilon;       /* SDF.epsilon 1e-3                                                 */
   float max_t;         /* intersect(max_t=10)                                              */
-  int32_t primary;     /* 1: run the 128-step coarse scan (SDF.throughput, sdfs.py:232)     */
+  int32_t primary;     /* 0: no scan; 1: the 128-step coarse scan (SDF.throughput, sdfs.py:232);
+                          2: the alpha scan (below)                                          */
   double scan_max_t;   /* dist + random.random()*(2/128), computed by the caller           */
   int32_t precision;   /* NRT_FP32 / NRT_FP16 / NRT_FP32_SPLIT / NRT_MIXED                  */
   int32_t* scan_index; /* optional [P] output: the coarse-scan argmin idxs (sdfs.py:243-246), so a
@@ -266,7 +267,30 @@ typedef struct {
  *   raw_n (un-normalised gradient, 0 on misses; may be NULL), wi = to_local(-d) (NULL ok),
  *   throughput (-1000*sdf(best scan point); untouched when primary == 0).
  * hit_idx[P] / hit_count[1] (int32, optional): compacted indices of hit rays (any order).
- * workspace: nrt_intersect_workspace_bytes(P) bytes of device memory. */
+ * workspace: nrt_intersect_workspace_bytes(P) bytes of device memory.
+ *
+ * primary = 2, the alpha scan: the caller promises that only sigmoid(throughput) in f32 will be
+ * read (nrt_composite's alpha, 1.f / (1.f + expf(-thr))).  That expression is exactly 1.0f from
+ * thr = 17.33 on (expf(-thr) < 2^-25), and thr = -1000 sdf(best), so a ray's alpha is decided as
+ * soon as one scan sample has d <= -0.02f (the one sample test, used everywhere):
+ *   - throughput[r] is the exact value wherever the ray's scan minimum is above -0.02;
+ *   - it is the constant 20.0f wherever some scan sample is <= -0.02;
+ *   - either way 1 / (1 + expf(-thr)) has the bits that primary = 1 gives;
+ *   - t, hit, p, n, raw_n, wi and the hit list do not depend on the mode;
+ *   - scan_index is valid only for rays whose throughput is not 20.0f.
+ * The margin from 17.33 to 20 is 2.67 logit units, 2.7e-3 in SDF units: it covers the FP16
+ * engine's SDF error (<= 7.3e-5, mixed_refine_d below) and the slightly different rounding of
+ * the point in the sdf(best) re-evaluation, so a precision that puts a sample on the other side
+ * of -0.02 still yields alpha 1.0f.  The non-MX ring marches (k_march32, k_march3, the plain
+ * k_march16) end a scan at its first such sample, start a hit ray's scan two grid points past its
+ * hit (wrapping around; the minimum is kept by (value, index), so the key does not depend on the
+ * order), and sdf(best) writes 20.0f from the scan's own key without an evaluation: the result
+ * does not depend on the schedule.  Engines without the early-out treat 2 as 1 -- the exact
+ * value satisfies the same promise: the per-wave k_intersect (option "ring32" = 0), the
+ * round-box / capsule kernels, NRT_MIXED (its refinement needs full keys and runner-ups), and
+ * the two march instantiations that are out of registers (the unfolded 256-wide k_march16, the
+ * 256-wide F = 32 k_march3); their sdf(best) still writes 20.0f for a saturated key.
+ * Option "scan_saturate" = 0 makes 2 mean 1 everywhere. */
 size_t nrt_intersect_workspace_bytes(const nrt_sdf* sdf, int64_t P);
 int nrt_sdf_intersect(const nrt_sdf* sdf, const float* rays, int64_t P,
                       const nrt_march_params* params, float* t, uint8_t* hit, float* p, float* n,
@@ -463,7 +487,9 @@ int nrt_composite(const float* rgb, const float* throughput, const uint8_t* hit,
  * jitter); with_alpha = 1 (NeRFIntegrator: channels 4, alpha = sigmoid(throughput), misses kept)
  * or 0 (Direct: channels 3, misses = background).  workspace: nrt_render_tile_workspace_bytes
  * bytes of device memory (every intermediate; nothing is allocated).  The same launches as the
- * Python chain render.render_tile, so the results are bit-identical. */
+ * Python chain render.render_tile, so the results are bit-identical: as there, the scan's only
+ * reader is the composite, so a non-zero params->primary runs as the alpha scan (2) with alpha
+ * and as no scan (0) without. */
 size_t nrt_render_tile_workspace_bytes(const nrt_sdf* sdf, int32_t N, int32_t W, int32_t H);
 int nrt_render_tile(const nrt_camera* host_cams, int32_t N, int32_t x0, int32_t y0, int32_t W,
                     int32_t H, float with_noise, const float* noise, const nrt_sdf* sdf,
@@ -535,7 +561,10 @@ int nrt_profile_read(const char* name, double* total_ms, int64_t* launches);
 /* SDF evaluations (ray x point) the ring marches (k_march16 / k_scan_best16 / k_march32 /
  * k_scan_best32) executed while NRT_PROF_EVALS was enabled, since the last nrt_profile_reset: the
  * executed work behind the algorithmic count (every ray at every march step and scan point,
- * sdfs.py:119-131, 232-249), which the lane-level job lists lower.  Synchronises. */
+ * sdfs.py:119-131, 232-249), which the lane-level job lists lower.  A primary = 1 ray counts its
+ * live march steps + 129 scan samples + sdf(best); a primary = 2 ray its march steps + the
+ * samples up to its first one <= -0.02 (all 129, and sdf(best), only where there is none).
+ * Synchronises. */
 int nrt_profile_evals(uint64_t* evals);
 /* Rays the NRT_MIXED refinement re-marched on the split engine (the flagged rays, nrt_ring_mixed
  * step 2) while NRT_PROF_EVALS was enabled, since the last nrt_profile_reset.  Synchronises. */
@@ -635,6 +664,10 @@ int nrt_profile_flop(const char* name, double* flop);
  *                      copy of the table staged once per block; 0: the per-wave kernels (32 rays
  *                      a wave) on the same device functions.  The same bits for every value (a
  *                      ray's values do not depend on the schedule)
+ *   "scan_saturate"  1  nrt_march_params.primary = 2 runs the alpha scan (nrt_sdf_intersect: scans
+ *                      end at their first sample <= -0.02, sdf(best) writes 20.0f for such a
+ *                      key); 0: 2 means 1, the exact scan -- the same sigmoid(throughput) bits,
+ *                      for an A/B in one build and for callers that read the throughput itself
  * nrt_set_option returns NRT_EINVAL for an unknown name or a negative value.
  * ------------------------------------------------------------------------------------- */
 int nrt_set_option(const char* name, int64_t value);

@@ -221,7 +221,11 @@ int nrt_sdf_intersect(const nrt_sdf* s, const float* rays, int64_t P, const nrt_
   ma.max_steps = a->max_steps;
   ma.eps = a->epsilon;
   ma.max_t = a->max_t;
-  ma.primary = a->primary;
+  ma.primary = a->primary ? 1 : 0;
+  // primary = 2, the alpha scan: the non-MX ring marches end a scan at its first saturating
+  // sample; every other engine (and option "scan_saturate" = 0) runs the exact scan, which
+  // satisfies the same promise
+  ma.sat = (a->primary == 2 && !mixed && option(OPT_SCAN_SATURATE) != 0) ? 1 : 0;
   ma.xcd_lines = (int)option(OPT_XCD_LINES);
   ma.step = a->scan_max_t / 128.0;
   ma.scan_idx = a->primary ? a->scan_index : nullptr;

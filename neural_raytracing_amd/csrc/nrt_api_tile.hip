@@ -77,8 +77,12 @@ int nrt_render_tile(const nrt_camera* host_cams, int32_t N, int32_t x0, int32_t 
   hipStream_t st = (hipStream_t)stream;
   if (int rc = nrt_raygen(host_cams, N, x0, y0, W, H, with_noise, noise, nullptr, w.rays, stream))
     return rc;
-  const bool primary = params->primary != 0;
-  if (int rc = nrt_sdf_intersect(sdf, w.rays, P, params, w.t, w.hit, w.p, w.n, w.raw, w.wi,
+  // the scan's only reader here is the composite's sigmoid(throughput): with alpha the alpha
+  // scan (primary = 2) serves it, without alpha nothing reads the throughput and the scan goes
+  nrt_march_params mp = *params;
+  mp.primary = (params->primary != 0 && with_alpha) ? 2 : 0;
+  const bool primary = mp.primary != 0;
+  if (int rc = nrt_sdf_intersect(sdf, w.rays, P, &mp, w.t, w.hit, w.p, w.n, w.raw, w.wi,
                                  primary ? w.thr : nullptr, w.idx, w.cnt, w.iws, stream))
     return rc;
   // Direct.sample leaves misses black (integrators.py:156-206); without the scan the throughput

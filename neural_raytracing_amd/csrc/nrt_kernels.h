@@ -311,7 +311,16 @@ struct MarchArgs {
   // launch-queue march (mode 0, packed t): byte offset in the block's LDS of the per-wave line
   // stages (LineStage, kStageBytes a wave); 0 = every finished ray stores its own words
   int stage = 0;
+  // nrt_march_params.primary = 2 (alpha scan, option "scan_saturate"; the non-MX ring marches):
+  // a scan job ends at its first sample d <= kScanSat, a non-tail ray's march becomes its own scan
+  // job (a hit starts near t, wrapping around), and sdf(best) writes kSatThr for a key whose
+  // value is <= kScanSat without evaluating.  Wave-uniform.
+  int sat = 0;
 };
+// the alpha scan's sample test, d <= kScanSat (thr = -1000 d >= 20: sigmoid(thr) is 1.0f in f32
+// from 17.33 on), and the throughput written for a ray that has such a sample
+constexpr float kScanSat = -0.02f;
+constexpr float kSatThr = 20.0f;
 #ifndef NRT_QUEUE_CHUNK
 #define NRT_QUEUE_CHUNK 16
 #endif
@@ -332,10 +341,12 @@ constexpr int kQueueTail = NRT_QUEUE_TAIL;    // rays per wave of the grid whose
 // ends is written with the lanes of its finished rays only.  Every ray's word is written exactly
 // once either way: the same bits as the per-ray stores.  The slot table (line, finished-ray mask)
 // lives in lanes 0 .. kStageSlots-1 of two VGPRs; all control is wave-uniform.
-// Only the packed t's stage can evict: marches differ in length, so a wave may hold rays of many
-// lines.  The key stage cannot -- every whole scan is 129 evaluations long and a wave takes a
-// line's 16 scans in order, so at most two key lines are open at once; its eviction branch is the
-// same code and is covered by the t stage's test (tests/test_gpu_line_stage.py).
+// The packed t's stage evicts: marches differ in length, so a wave may hold rays of many lines.
+// The key stage does not under the exact scan (primary = 1) -- every whole scan is 129
+// evaluations long and a wave takes a line's 16 scans in order, so at most two key lines are open
+// at once.  Under the alpha scan (MarchArgs::sat) a key finishes after its ray's march plus 1 to
+// 129 samples, out of ray order, so the key stage holds many open lines and evicts like the t
+// stage; it is the same code (tests/test_gpu_line_stage.py, tests/test_gpu_scan_saturate.py).
 constexpr int kStageSlots = 8;
 constexpr int kStageBytes = kStageSlots * 16 * (4 + 8);  // t words, then key words
 template <class W>
@@ -617,6 +628,9 @@ struct RingPol16 {
   }
   __device__ __forceinline__ static void finish(Eng&) {}
   static constexpr bool kGuard = false;
+  // the alpha scan's early-out in the march (MarchArgs::sat): compiled out of the 256-wide
+  // unfolded march, which spills already and would spill more (it runs the exact scan instead)
+  static constexpr bool kSat = FOLD || NB < 8;
   __device__ __forceinline__ static bool retry(Eng&, bool, float) { return false; }
 };
 template <int KH, int KE, int WV, int ACT>
@@ -637,6 +651,7 @@ struct RingPol32 {
   }
   __device__ __forceinline__ static void finish(Eng& E) { E.drain(); }
   static constexpr bool kGuard = false;
+  static constexpr bool kSat = true;
   __device__ __forceinline__ static bool retry(Eng&, bool, float) { return false; }
 };
 
@@ -667,6 +682,7 @@ struct RingPol3 {
   }
   __device__ __forceinline__ static void finish(Eng& E) { E.drain(); }
   static constexpr bool kGuard = true;
+  static constexpr bool kSat = !(KH == 8 && KQ == 3);  // (as RingPol16: that march spills)
   __device__ __forceinline__ static bool retry(Eng& E, bool active, float v) {
     return ring3::retry(E, active, v);
   }
@@ -708,7 +724,11 @@ __device__ __forceinline__ void march_body(
   // sdf(best) with a runner-up key: a second job per ray re-evaluates the runner-up where the
   // FP16 scan could not order the two (skipped elsewhere)
   const bool alt = MX && mode == 1 && a.keys2 != nullptr;
-  const int64_t J = mode == 0 ? (scan ? R + (R - T) + T * kScanSegs : R) : (alt ? 2 * R : R);
+  // alpha scan (MarchArgs::sat): no whole-scan entries -- a ray of [0, R - T) is scanned by the
+  // lane that marched it, so the list is [march of every ray][segments of the last T rays]
+  // (sdf(best) decides on the key alone, so it need not know whether its march took the early-out)
+  const bool sat = !MX && (mode == 1 || (mode == 0 && Pol::kSat)) && a.sat != 0;
+  const int64_t J = mode == 0 ? (scan ? R + (sat ? 0 : R - T) + T * kScanSegs : R) : (alt ? 2 * R : R);
   const uint32_t lt = (1u << r) - 1u;
   typename Pol::Eng E;
   Pol::init(E, s, m, smem_c, a);
@@ -718,7 +738,9 @@ __device__ __forceinline__ void march_body(
   float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
   float t = 0.f, best = 0.f, second = 0.f;
   double step = a.step;  // this lane's scan step (per tile group when batched)
-  int i = 0, j = 0, jend = 0, idx = 0, idx2 = 0;
+  // a scan job: sample j next, `left` samples to go (j wraps from 128 to 0: the alpha scan of a
+  // hit ray starts near the hit); `whole` also marks a march whose lane goes on to scan its ray
+  int i = 0, j = 0, left = 0, idx = 0, idx2 = 0;
   bool ended = false, hit = false, whole = false;
   unsigned long long ambs = ~0ull;  // NRT_MIXED: the first undecidable step's (i, t), or none
   float drift = 0.f, dprev = 1.f;   // NRT_MIXED: t's drift bound (units of the FP16 error)
@@ -774,9 +796,19 @@ __device__ __forceinline__ void march_body(
             }
           }
           kind = -1;
+          if (mode == 0 && sat && whole) {
+            // alpha scan: this lane scans the ray it marched (origin, direction and step are in
+            // its registers).  A hit's saturating samples lie just past t, so it starts two grid
+            // points beyond and wraps around; a miss walks up from 0.  Any start gives the same
+            // key: the minimum is kept by (value, index), not by visiting order.
+            kind = 1;
+            j = hit ? (int)fminf(fmaxf(t / (float)step, 0.f), 126.f) + 2 : 0;
+            left = 16 * kScanSegs + 1;
+            idx = -1;
+          }
         }
       } else if (kind == 1) {
-        if (j > jend) {
+        if (left == 0) {
           // a whole scan stores its key; a segment merges into it (all segments of a ray are
           // in this wave's list; the key buffer starts at all-ones)
           if (lane < RPW) {
@@ -831,10 +863,10 @@ __device__ __forceinline__ void march_body(
           int seg = -1;  // -1 march, kScanSegs whole scan, else a segment
           if (mode == 0 && q >= R) {
             k = q - R;
-            if (k < R - T) {
+            if (!sat && k < R - T) {
               seg = kScanSegs;
             } else {
-              k -= R - T;
+              if (!sat) k -= R - T;
               seg = (int)(k / T);
               k = R - T + (k - (int64_t)seg * T);
             }
@@ -859,6 +891,12 @@ __device__ __forceinline__ void march_body(
             kind = 2;
             const unsigned long long k1 = keys[ray];
             idx = (int)(uint32_t)k1;
+            if (sat && scan_key_value(k1) <= kScanSat) {
+              // alpha scan: decided on the scan's own key (never on a re-evaluated value), so the
+              // throughput does not depend on which job scanned the ray; no evaluation
+              if (lane < RPW) thr_out[ray] = kSatThr;
+              kind = -1;
+            }
             if (second_job) {
               // the runner-up only where the FP16 values of the two lie within refine_s
               const unsigned long long k2 = a.keys2[ray];
@@ -867,6 +905,7 @@ __device__ __forceinline__ void march_body(
             }
           } else if (seg < 0) {
             kind = 0; t = 0.f; i = 0; hit = false; ambs = ~0ull; drift = 0.f; cps = ~0ull;
+            whole = mode == 0 && sat && scan && k < R - T;  // (the tail's scans stay segments)
             if (mode == 3) {  // shadow rays start 100 eps out (sdfs.py:170)
               t = 0.f + 1e2f * a.eps;
               mt = a.occ_max_t[ray];
@@ -880,7 +919,7 @@ __device__ __forceinline__ void march_body(
             kind = 1;
             whole = seg == kScanSegs;
             j = (seg == 0 || whole) ? 0 : 16 * seg + 1;
-            jend = whole ? 16 * kScanSegs : 16 * seg + 16;
+            left = (whole ? 16 * kScanSegs : 16 * seg + 16) - j + 1;
             idx = -1;
           }
         } else if (!dyn) {
@@ -953,10 +992,14 @@ __device__ __forceinline__ void march_body(
         else if (d < second) { second = d; idx2 = j; }
         best = fminf(best, d);
       } else {
-        if (d < best) idx = j;
+        // the minimum of scan_key(d, j): lowest value, then lowest index (a wrapped scan meets
+        // low indices last; in ascending order the second test never holds)
+        if (d < best || (d == best && j < idx)) idx = j;
         best = fminf(best, d);
       }
-      ++j;
+      j = j == 16 * kScanSegs ? 0 : j + 1;
+      --left;
+      if (sat && d <= kScanSat) left = 0;  // alpha scan: the ray's alpha is decided
     } else if (kind == 2) {
       if (lane < RPW) {
         if (MX && mode == 1 && a.kbest)  // both candidates of a ray merge; k_scan_pick writes thr

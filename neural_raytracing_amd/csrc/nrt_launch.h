@@ -40,6 +40,7 @@ enum Option {
   OPT_WGRAD_TILE,      // "wgrad_tile"
   OPT_MARCH_STAGE,     // "march_stage"
   OPT_PRIM_MARCH,      // "prim_march"
+  OPT_SCAN_SATURATE,   // "scan_saturate"
   OPT_COUNT
 };
 int64_t option(Option o);

@@ -64,7 +64,15 @@ def direct_kernels(direct, shapes, rays_flat, bsdf, lights, scan_groups=None, w_
     scan_draws: those G uniforms already drawn by the caller (render_tiles draws every tile's,
     the ones a rank does not render included, so the frame does not depend on the world size).
     w_isect: Direct's emitter sample with a shadow ray (True) or a learned occlusion MLP, as
-    Direct.sample picks it (integrators.py:161-166)."""
+    Direct.sample picks it (integrators.py:161-166).
+    direct: the Direct integrator, or fused_integrator's pair (direct, with_alpha), which says
+    what the composite will read of the scan -- with alpha only sigmoid(throughput), so the march
+    runs the alpha scan (nrt_march_params.primary = 2); without alpha nothing, so no scan runs
+    (b.thr is zero).  A bare Direct gets the exact throughput (primary = 1).  The scan jitter is
+    drawn in every case, so python's RNG state afterwards is the reference's."""
+    with_alpha = None
+    if isinstance(direct, tuple):
+        direct, with_alpha = direct[:2]
     P = rays_flat.shape[0]
     dev = rays_flat.device
     nb = len(getattr(bsdf, "bsdfs", [bsdf]))
@@ -86,9 +94,11 @@ def direct_kernels(direct, shapes, rays_flat, bsdf, lights, scan_groups=None, w_
         else:
             groups = torch.tensor([dist + u * (2 / 128) for u in scan_draws],
                                   dtype=torch.float64).to(dev, non_blocking=True)
+    if primary and with_alpha is not None:
+        primary = 2 if with_alpha else 0
     mp = _lib.MarchParams(int(shapes.max_steps), float(shapes.epsilon), 10.0, int(primary),
                           float(scan_max_t), _lib.precision_code())
-    if groups is not None:
+    if groups is not None and primary:
         mp.scan_max_t_groups = groups.data_ptr()
         mp.group_rays = P // scan_groups
     s = _lib.stream()
@@ -126,7 +136,7 @@ def render_tile(fused, shapes, lights, cameras, bsdf, out, x0, y0, chunk, size, 
     direct, with_alpha = fused
     rays = cameras.rays_tile(x0, y0, chunk, chunk, size, with_noise)
     N = rays.shape[0]
-    b = direct_kernels(direct, shapes, rays.reshape(-1, 6), bsdf, lights)
+    b = direct_kernels((direct, with_alpha), shapes, rays.reshape(-1, 6), bsdf, lights)
     composite(b, N, chunk, chunk, with_alpha, background, out, x0 - ox, y0 - oy)
     return b
 
@@ -174,7 +184,7 @@ def render_tiles(fused, shapes, lights, cameras, bsdf, out, tiles, chunk, size, 
             rays[k] = r.reshape(-1, 6)
         if per_tile == 0:
             continue  # (no rows of these tiles here: their draws are taken, nothing to render)
-        b = direct_kernels(direct, shapes, rays.reshape(-1, 6), bsdf, lights,
+        b = direct_kernels((direct, with_alpha), shapes, rays.reshape(-1, 6), bsdf, lights,
                            scan_groups=len(batch) if len(batch) > 1 else None, w_isect=w_isect,
                            scan_draws=[scan[ti] for ti in batch] if primary else None)
         for k, ti in enumerate(batch):
@@ -305,7 +315,8 @@ class RowRenderer:
         rays = self.cameras.rays_tile(0, 0, R, self.size, self.size, self.with_noise,
                                       positions=self.positions)
         N = rays.shape[0]
-        b = direct_kernels(direct, self.shapes, rays.reshape(-1, 6), self.bsdf, self.lights)
+        b = direct_kernels((direct, with_alpha), self.shapes, rays.reshape(-1, 6), self.bsdf,
+                           self.lights)
         composite(b, N, R, self.size, with_alpha, self.background, self.image, 0, 0)
         return self.image
 
