@@ -359,10 +359,40 @@ typedef struct {
   float params[4];       /* DIFFUSE: reflectance rgb; CONDUCTOR: specular rgb, eta         */
 } nrt_bsdf_component;
 
+#define NRT_BSDF_PHONG 3      /* Phong (bsdfs.py:132-189)                                   */
+#define NRT_BSDF_PLASTIC 4    /* Plastic (bsdfs.py:238-325)                                 */
+#define NRT_BSDF_PARAMS 12
+
+/* A component with the wider parameter block of the analytic models, and Bidirectional
+ * (bsdfs.py:409-453).  params per kind (host-computed constants as the reference computes them,
+ * in Python doubles, before the tensor arithmetic):
+ *   DIFFUSE    reflectance rgb                       CONDUCTOR  specular rgb, softplus(eta)
+ *   PHONG      diffuse rgb, specular rgb, min_spec + exp(shine)            (:181)
+ *   PLASTIC    diffuse rgb, specular rgb, eta, 1/eta, 1 - fdr_int, inv_eta_2,
+ *              spec_sample_weight = mean(specular) / (mean(diffuse) + mean(specular))  (:254-265)
+ * two_sided != 0: the component is Bidirectional(front, back): the front model where wi.z > 0,
+ * the back model at (invert_z(wi), invert_z(wo)) where wi.z < 0, zero at wi.z == 0.  A NEURAL
+ * front has the same MLP on both sides (back_kind NEURAL; a distinct back MLP is not supported);
+ * an analytic front takes any analytic back.  Unused params must be finite (0). */
+typedef struct {
+  int32_t kind;
+  const nrt_mlp* mlp;
+  int32_t activation;
+  float params[NRT_BSDF_PARAMS];
+  int32_t two_sided;
+  int32_t back_kind;
+  int32_t back_activation;
+  float back_params[NRT_BSDF_PARAMS];
+} nrt_bsdf_component_ex;
+
 /* ComposeSpatialVarying (bsdfs.py:482-536): sum_j sigmoid(sp_var(p))_j * f_j.
- * spatial may be NULL for a single component (weight 1, no sigmoid). */
+ * spatial may be NULL for a single component (weight 1, no sigmoid).
+ * nrt_bsdf_create builds the same handle from one-sided components with params[0..3] and keeps
+ * its checks (kind, MLP shape); nrt_bsdf_create_ex also checks every activation and parameter. */
 int nrt_bsdf_create(int32_t n, const nrt_bsdf_component* components, const nrt_mlp* spatial,
                     nrt_bsdf** out);
+int nrt_bsdf_create_ex(int32_t n, const nrt_bsdf_component_ex* components, const nrt_mlp* spatial,
+                       nrt_bsdf** out);
 int nrt_bsdf_destroy(nrt_bsdf* bsdf);
 
 /* Direct.sample's emitter + BSDF block (integrators.py:173-189) for the hit rays listed in
@@ -374,6 +404,17 @@ int nrt_shade_direct(const nrt_bsdf* bsdf, const nrt_light* light, const float* 
                      const float* n, const float* wi, const int32_t* hit_idx,
                      const int32_t* hit_count, int64_t P, float* rgb, float* weights_out,
                      int precision, void* stream);
+
+/* ComposeSpatialVarying.eval_and_pdf (bsdfs.py:515-528) at a caller-supplied local wo [P, 3], the
+ * standalone form of the BSDF block above (BSDF.eval_and_pdf of bsdf/bsdfs.py; plotting a lobe,
+ * a custom integrator): spectrum[i] = sum_j k_j f_j(wi, wo), pdf[i] = sum_j k_j pdf_j, both zero
+ * where active[i] == 0 (active NULL: every ray).  weights_out [P, n_components] (optional) as
+ * nrt_shade_direct, written for the active rays.  A prep kernel writes the light stage's record
+ * (Le = 1, the features of (wi, wo), wo) and the BSDF stage of nrt_shade_direct runs on it, on
+ * the same engine at each precision. */
+int nrt_bsdf_eval(const nrt_bsdf* bsdf, const float* p, const float* n, const float* wi,
+                  const float* wo, const uint8_t* active, int64_t P, float* spectrum, float* pdf,
+                  float* weights_out, int precision, void* stream);
 
 /* Direct.sample with w_isect=True (integrators.py:163 -> sample_emitter_dir_w_isect,
  * scene.py:290-298): for each listed hit ray, a point-light sample, a shadow ray
@@ -418,6 +459,18 @@ int nrt_path_bounce(const nrt_bsdf* bsdf, const nrt_light* light, const nrt_sdf*
                     const float* p, const float* n, const float* wi, int64_t P, uint8_t* active,
                     float* throughput, float* result, const float* u_comp, const float* u_sel,
                     float* rays_out, void* workspace, int precision, void* stream);
+/* nrt_path_bounce with Phong.sample (bsdfs.py:155-175) and Plastic.sample (:292-325) components:
+ * u_lobe [P, n_components] holds Plastic's specular / diffuse draw (sampler.sample(p_spec.shape),
+ * :304, drawn before the component's (.., 2) draw); it is read for Plastic components only and may
+ * be NULL when the mixture has none (NULL with one: NRT_EINVAL).  A two-sided component is
+ * refused (NRT_EUNSUPPORTED): Bidirectional.sample fails in the reference (combine() without its
+ * masks, :432 against :26).  nrt_path_bounce forwards here with u_lobe NULL. */
+int nrt_path_bounce_ex(const nrt_bsdf* bsdf, const nrt_light* light, const nrt_sdf* sdf,
+                       int32_t shadow, const nrt_mlp* occ, int32_t max_steps, float epsilon,
+                       const float* p, const float* n, const float* wi, int64_t P,
+                       uint8_t* active, float* throughput, float* result, const float* u_comp,
+                       const float* u_sel, const float* u_lobe, float* rays_out, void* workspace,
+                       int precision, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Cameras (cameras/cameras.py) and the tile composite (main.py:85-90, integrators.py:251)

@@ -23,6 +23,8 @@ _PRECISIONS = {"fp32": NRT_FP32, "fp16": NRT_FP16, "fp32-split": NRT_FP32_SPLIT,
 ACT = {"leaky_relu": 0, "softplus": 1, "none": 2, "sigmoid": 3, "relu": 4}
 
 NRT_BSDF_NEURAL, NRT_BSDF_DIFFUSE, NRT_BSDF_CONDUCTOR = 0, 1, 2
+NRT_BSDF_PHONG, NRT_BSDF_PLASTIC = 3, 4
+NRT_BSDF_PARAMS = 12
 NRT_CAM_NERF, NRT_CAM_DTU, NRT_CAM_FOV = 0, 1, 2
 
 
@@ -46,6 +48,15 @@ class MarchParams(ctypes.Structure):
 class BsdfComponent(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("mlp", ctypes.c_void_p),
                 ("activation", ctypes.c_int32), ("params", ctypes.c_float * 4)]
+
+
+class BsdfComponentEx(ctypes.Structure):
+    """nrt_bsdf_component_ex (include/nrt.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("mlp", ctypes.c_void_p),
+                ("activation", ctypes.c_int32), ("params", ctypes.c_float * NRT_BSDF_PARAMS),
+                ("two_sided", ctypes.c_int32), ("back_kind", ctypes.c_int32),
+                ("back_activation", ctypes.c_int32),
+                ("back_params", ctypes.c_float * NRT_BSDF_PARAMS)]
 
 
 class Camera(ctypes.Structure):
@@ -103,7 +114,9 @@ _SIGNATURES = {
     "nrt_sphere_cloud_intersect": (_I32, [_P, _I64, _I64, ctypes.c_double, _P, _I64, _P, _P, _P, _P,
                                           _P, _P, _P]),
     "nrt_bsdf_create": (_I32, [_I32, _P, _P, ctypes.POINTER(_P)]),
+    "nrt_bsdf_create_ex": (_I32, [_I32, _P, _P, ctypes.POINTER(_P)]),
     "nrt_bsdf_destroy": (_I32, [_P]),
+    "nrt_bsdf_eval": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _P]),
     "nrt_shade_direct": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I32, _P]),
     "nrt_shadow_workspace_bytes": (ctypes.c_size_t, [_I64]),
     "nrt_shade_direct_shadowed": (_I32, [_P, _P, _P, _I32, _F, _P, _P, _P, _P, _P, _I64, _P, _P,
@@ -114,6 +127,8 @@ _SIGNATURES = {
     "nrt_path_workspace_bytes": (ctypes.c_size_t, [_I64]),
     "nrt_path_bounce": (_I32, [_P, _P, _P, _I32, _P, _I32, _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                                _P, _P, _I32, _P]),
+    "nrt_path_bounce_ex": (_I32, [_P, _P, _P, _I32, _P, _I32, _F, _P, _P, _P, _I64, _P, _P, _P, _P,
+                                  _P, _P, _P, _P, _I32, _P]),
     "nrt_render_tile_workspace_bytes": (ctypes.c_size_t, [_P, _I32, _I32, _I32]),
     "nrt_render_tile": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P,
                                ctypes.POINTER(MarchParams), _P, _P, _I32, _F, _P, _I32, _I32, _I32,

@@ -5,7 +5,8 @@
 
 namespace nrt {
 
-// warps.py:10-30 (output (r sin phi, r cos phi), as written there) and :44-49
+// warps.py:10-30 (output (r sin phi, r cos phi), as written there) and :44-49; the callers
+// normalize where the reference's sample() does (NeuralBSDF :629, Diffuse :99; not Phong, Plastic)
 __device__ __forceinline__ void cos_hemisphere(float u0, float u1, float wo[3]) {
   const float vx = 2.f * u0 - 1.f, vy = 2.f * u1 - 1.f;
   const bool zero = vx == 0.f && vy == 0.f;
@@ -20,7 +21,6 @@ __device__ __forceinline__ void cos_hemisphere(float u0, float u1, float wo[3]) 
   const float px = r * sinf(phi), py = r * cosf(phi);
   const float z = sqrtf(fmaxf(1.f - (px * px + py * py), 1e-7f));
   wo[0] = px; wo[1] = py; wo[2] = z;
-  normalize3(wo[0], wo[1], wo[2], 1e-12f);
 }
 
 // from_local (interaction.py:44-51): normalize(s x + t y + n z), f = [s | t | n] columns
@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) k_path_sample(
     const BsdfDev* __restrict__ bp, const float* __restrict__ P_, const float* __restrict__ N_,
     const float* __restrict__ WI, const int32_t* __restrict__ list, const int32_t* __restrict__ count,
     const float* __restrict__ rgb, const float* __restrict__ u_comp, const float* __restrict__ u_sel,
-    uint8_t* __restrict__ active, float* __restrict__ thr, float* __restrict__ result,
+    const float* __restrict__ u_lobe, uint8_t* __restrict__ active, float* __restrict__ thr, float* __restrict__ result,
     float* __restrict__ rays, int RS, int per_wave) {
   extern __shared__ float smem[];
   const BsdfDev& bs = *bp;
@@ -82,6 +82,7 @@ __global__ void __launch_bounds__(256) k_path_sample(
         const float* u = u_comp + (idx * nc + job) * 2;
         cos_hemisphere(u[0], u[1], wo);
       }
+      if (m && job >= 0) normalize3(wo[0], wo[1], wo[2], 1e-12f);
       if (m) {
         EncIn e;
         e.xg = nullptr; e.lat = nullptr; e.x[3] = 0.f;
@@ -112,9 +113,11 @@ __global__ void __launch_bounds__(256) k_path_sample(
         if (c.kind == 0) {
           for (int q = 0; q < 3; ++q) sel_f[q] = act_fwd<false>(l.Y[r * ys + q], c.act);
         } else {
-          // Diffuse.sample: spectrum = preproc(reflectance) (bsdfs.py:104)
-          for (int q = 0; q < 3; ++q)
-            sel_f[q] = (c.act == ACT_NONE) ? c.params[q] / (float)M_PI : act_fwd<false>(c.params[q], c.act);
+          const float nrm[3] = {fr[2], fr[5], fr[8]};
+          const float ul = c.kind == NRT_BSDF_PLASTIC ? u_lobe[idx * nc + job] : 0.f;
+          float ws[3];
+          bsdf_model_sample(c, nrm, wix, wiy, wiz, wo, ul, sel_f, ws);
+          wo[0] = ws[0]; wo[1] = ws[1]; wo[2] = ws[2];
         }
         sel_wo[0] = wo[0]; sel_wo[1] = wo[1]; sel_wo[2] = wo[2];
       }
@@ -159,17 +162,38 @@ int nrt_path_bounce(const nrt_bsdf* b, const nrt_light* l, const nrt_sdf* s, int
                     int64_t P, uint8_t* active, float* throughput, float* result,
                     const float* u_comp, const float* u_sel, float* rays_out, void* workspace,
                     int precision, void* stream) {
+  return nrt_path_bounce_ex(b, l, s, shadow, occ, max_steps, eps, p, n, wi, P, active, throughput,
+                            result, u_comp, u_sel, nullptr, rays_out, workspace, precision, stream);
+}
+
+int nrt_path_bounce_ex(const nrt_bsdf* b, const nrt_light* l, const nrt_sdf* s, int32_t shadow,
+                       const nrt_mlp* occ, int32_t max_steps, float eps, const float* p,
+                       const float* n, const float* wi, int64_t P, uint8_t* active,
+                       float* throughput, float* result, const float* u_comp, const float* u_sel,
+                       const float* u_lobe, float* rays_out, void* workspace, int precision,
+                       void* stream) {
   if (!b || !l || !p || !n || !wi || P < 0 || !active || !throughput || !result || !u_comp ||
       !u_sel || !rays_out || !workspace || (shadow && !s)) {
     set_error("nrt_path_bounce: bad argument");
     return NRT_EINVAL;
   }
-  for (int j = 0; j < b->host_dev.n; ++j)
+  for (int j = 0; j < b->host_dev.n; ++j) {
     if (b->host_dev.comp[j].kind == NRT_BSDF_CONDUCTOR) {
       set_error("nrt_path_bounce: Conductor.sample is not defined (it fails in the reference, "
                 "bsdfs.py:391-401)");
       return NRT_EUNSUPPORTED;
     }
+    if (b->host_dev.comp[j].two_sided) {
+      set_error("nrt_path_bounce: Bidirectional.sample is not defined (it fails in the reference: "
+                "BSDFSample.combine is called without its masks, bsdfs.py:432 against :26)");
+      return NRT_EUNSUPPORTED;
+    }
+  }
+  if (b->host_dev.has_plastic && !u_lobe) {
+    set_error("nrt_path_bounce: a Plastic component needs u_lobe [P, n_components] "
+              "(nrt_path_bounce_ex)");
+    return NRT_EINVAL;
+  }
   if (P == 0) return NRT_OK;
   hipStream_t st = (hipStream_t)stream;
   const bool f16 = precision == NRT_FP16;
@@ -205,12 +229,12 @@ int nrt_path_bounce(const nrt_bsdf* b, const nrt_light* l, const nrt_sdf* s, int
   if (f16) {
     if ((rc = set_lds(k_path_sample<true>, lp.bytes))) return rc;
     k_path_sample<true><<<dim3(blocks), dim3(64 * lp.waves), lp.bytes, st>>>(
-        b->dev, p, n, wi, list, cnt, rgb, u_comp, u_sel, active, throughput, result, rays_out,
+        b->dev, p, n, wi, list, cnt, rgb, u_comp, u_sel, u_lobe, active, throughput, result, rays_out,
         lp.RS, lp.per_wave);
   } else {
     if ((rc = set_lds(k_path_sample<false>, lp.bytes))) return rc;
     k_path_sample<false><<<dim3(blocks), dim3(64 * lp.waves), lp.bytes, st>>>(
-        b->dev, p, n, wi, list, cnt, rgb, u_comp, u_sel, active, throughput, result, rays_out,
+        b->dev, p, n, wi, list, cnt, rgb, u_comp, u_sel, u_lobe, active, throughput, result, rays_out,
         lp.RS, lp.per_wave);
   }
   return check_launch("k_path_sample");

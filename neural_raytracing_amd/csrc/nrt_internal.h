@@ -94,15 +94,24 @@ struct LightDev {
 
 constexpr int kMaxComponents = 32;
 
+constexpr int kBsdfParams = 12;  // == NRT_BSDF_PARAMS (nrt.h has the per-kind layout)
+
 struct BsdfCompDev {
   int kind;
   const MlpDev* mlp;
   int act;
-  float params[4];
+  float params[kBsdfParams];
+  // Bidirectional (bsdfs.py:409-453): the back model evaluates at (invert_z(wi), invert_z(wo))
+  // where wi.z < 0; a two-sided NeuralBSDF has back == front (one MLP)
+  int two_sided;
+  int back_kind, back_act;
+  float back_params[kBsdfParams];
 };
 
 struct BsdfDev {
   int n;
+  int flip_feat;   // some NeuralBSDF component is two-sided: LS carries the flipped features
+  int has_plastic; // nrt_path_bounce_ex needs u_lobe
   const MlpDev* spatial;
   BsdfCompDev comp[kMaxComponents];
 };

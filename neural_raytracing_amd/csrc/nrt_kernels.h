@@ -1467,17 +1467,156 @@ __device__ __forceinline__ float fresnel_conductor(float cos_t, float eta_r) {
   return 0.5f * (rs + rp);
 }
 
+constexpr int kLsStride = 12;  // floats of an LS record (layout at k_light16 below)
+
+// ------------------------------------------------------------------------------------------
+// analytic BSDF models: the one evaluation (k_shade_direct, k_bsdf16, k_bsdf_r) and the one
+// sampling function (k_path_sample) of every component that is not a NeuralBSDF.  All f32 VALU.
+// ------------------------------------------------------------------------------------------
+// fresnel (bsdfs.py:193-218), its first result; inv_eta = 1 / eta from the host (a Python double
+// there, :197)
+__device__ __forceinline__ float fresnel_dielectric(float cos_t, float eta, float inv_eta) {
+  const bool out = cos_t >= 0.f;
+  const float eta_it = out ? eta : inv_eta, eta_ti = out ? inv_eta : eta;
+  // :200, through the reference's helper fnma(x, y, z) = -x * y + z (:194): a separate multiply
+  // and add, as here (the library is built without fp contraction)
+  const float cos_tt_sqr = -(-cos_t * cos_t + 1.f) * (eta_ti * eta_ti) + 1.f;
+  const float ca = fabsf(cos_t);
+  const float ct = sqrtf(fmaxf(cos_tt_sqr, 1e-10f));
+  const float a_s = (-eta_it * ct + ca) / (eta_it * ct + ca);
+  const float a_p = (-eta_it * ca + ct) / (eta_it * ca + ct);
+  float r = 0.5f * (a_s * a_s + a_p * a_p);
+  if (eta == 1.f) r = 0.f;       // :204-214: index-matched -> 0 everywhere,
+  else if (ca == 0.f) r = 1.f;   // else grazing incidence -> 1
+  return r;
+}
+
+// reflect(it.frame[..., 2], it.wi) (bsdfs.py:121-123): the WORLD normal against the LOCAL wi, as
+// Phong and Plastic.sample write it (:170, :180, :308)
+__device__ __forceinline__ void reflect_mixed(const float n[3], float wix, float wiy, float wiz,
+                                              float R[3]) {
+  const float d = 2.f * ((n[0] * wix + n[1] * wiy) + n[2] * wiz);
+  R[0] = d * n[0] - wix; R[1] = d * n[1] - wiy; R[2] = d * n[2] - wiz;
+}
+
+// eval_and_pdf of one analytic model.  n: normalised world normal (it.frame[..., 2]); wi, wo local.
+// pr: DIFFUSE reflectance rgb | CONDUCTOR specular rgb, eta | PHONG diffuse rgb, specular rgb,
+// exponent | PLASTIC diffuse rgb, specular rgb, eta, 1/eta, 1 - fdr_int, inv_eta_2, ssw
+__device__ __forceinline__ void bsdf_model_eval(int kind, int act, const float* pr, const float n[3],
+                                                float wix, float wiy, float wiz, float wo0,
+                                                float wo1, float wo2, float f[3], float& pdf) {
+  if (kind == NRT_BSDF_DIFFUSE) {
+    // Diffuse.eval_and_pdf (bsdfs.py:108-118)
+    for (int q = 0; q < 3; ++q) {
+      float x = wo2 * pr[q];
+      f[q] = (act == ACT_NONE) ? x / (float)M_PI : act_fwd<false>(x, act);
+    }
+    pdf = wo2 / (float)M_PI;
+  } else if (kind == NRT_BSDF_CONDUCTOR) {
+    // Conductor.eval_and_pdf (bsdfs.py:364-388)
+    float rx = -wix, ry = -wiy, rz = wiz;
+    bool th = ((rx * wo0 + ry * wo1) + rz * wo2) > 0.94f;
+    float fres = fresnel_conductor(wiz, pr[3]);
+    for (int q = 0; q < 3; ++q) f[q] = th ? fres * act_fwd<false>(pr[q], act) : 0.f;
+    pdf = th ? 1.f : 0.f;
+  } else if (kind == NRT_BSDF_PHONG) {
+    // Phong.eval_and_pdf (bsdfs.py:176-189); pr[6] = min_spec + exp(shine)
+    float R[3];
+    reflect_mixed(n, wix, wiy, wiz, R);
+    const float spectral = powf(fmaxf((R[0] * wo0 + R[1] * wo1) + R[2] * wo2, 1e-20f), pr[6]);
+    for (int q = 0; q < 3; ++q)
+      f[q] = wiz * pr[q] / (float)M_PI + spectral * pr[3 + q] / (float)M_PI;
+    pdf = wo2 / (float)M_PI;
+  } else {
+    // Plastic.eval_and_pdf (bsdfs.py:271-291)
+    const float f_i = fresnel_dielectric(wiz, pr[6], pr[7]);
+    const float f_o = fresnel_dielectric(wo2, pr[6], pr[7]);
+    const float pc = wo2 / (float)M_PI;
+    const float t = pc * (1.f - f_i) * (1.f - f_o);
+    for (int q = 0; q < 3; ++q) f[q] = (pr[q] / pr[8]) * pr[9] * t;
+    const float ssw = pr[10];
+    const float p_spec = ssw * f_i;
+    float p_diff = (1.f - f_i) * (1.f - ssw);
+    p_diff = p_diff / (p_spec + p_diff);
+    pdf = pc * p_diff;
+  }
+}
+
+// one component (not a NeuralBSDF) of the mixture, through Bidirectional when two-sided
+// (bsdfs.py:434-453): front where wi.z > 0, back at (invert_z(wi), invert_z(wo)) where wi.z < 0,
+// zero at wi.z == 0
+__device__ __forceinline__ void bsdf_comp_eval(const BsdfCompDev& c, const float n[3], float wix,
+                                               float wiy, float wiz, float wo0, float wo1,
+                                               float wo2, float f[3], float& pdf) {
+  if (!c.two_sided) {
+    bsdf_model_eval(c.kind, c.act, c.params, n, wix, wiy, wiz, wo0, wo1, wo2, f, pdf);
+    return;
+  }
+  const bool back = wiz < 0.f;
+  bsdf_model_eval(back ? c.back_kind : c.kind, back ? c.back_act : c.act,
+                  back ? c.back_params : c.params, n, wix, wiy, back ? -wiz : wiz, wo0, wo1,
+                  back ? -wo2 : wo2, f, pdf);
+  if (wiz == 0.f) { f[0] = 0.f; f[1] = 0.f; f[2] = 0.f; pdf = 0.f; }
+}
+
+// sample() of one analytic model for Path (bsdfs.py:90-106, 155-175, 292-325): the spectrum and
+// the local direction.  woc: square_to_cos_hemisphere of the component's draw (as warps.py
+// returns it, before any normalize); u_lobe: Plastic's specular / diffuse draw (:304).
+__device__ __forceinline__ void bsdf_model_sample(const BsdfCompDev& c, const float n[3], float wix,
+                                                  float wiy, float wiz, const float woc[3],
+                                                  float u_lobe, float f[3], float wo[3]) {
+  const float* pr = c.params;
+  wo[0] = woc[0]; wo[1] = woc[1]; wo[2] = woc[2];
+  if (c.kind == NRT_BSDF_DIFFUSE) {
+    // Diffuse.sample: spectrum = preproc(reflectance) (bsdfs.py:104)
+    for (int q = 0; q < 3; ++q)
+      f[q] = (c.act == ACT_NONE) ? pr[q] / (float)M_PI : act_fwd<false>(pr[q], c.act);
+    normalize3(wo[0], wo[1], wo[2], 1e-12f);  // :99
+  } else if (c.kind == NRT_BSDF_PHONG) {
+    // Phong.sample (bsdfs.py:155-175)
+    const float pdf = woc[2] / (float)M_PI;
+    float R[3];
+    reflect_mixed(n, wix, wiy, wiz, R);
+    const float spectral = powf(fmaxf((R[0] * woc[0] + R[1] * woc[1]) + R[2] * woc[2], 1e-20f), pr[6]);
+    const bool on = wiz > 0.f && woc[2] > 0.f && pdf > 0.f;
+    for (int q = 0; q < 3; ++q)
+      f[q] = on ? wiz * pr[q] / (float)M_PI + spectral * pr[3 + q] / (float)M_PI : 0.f;
+  } else {
+    // Plastic.sample (bsdfs.py:292-325)
+    const float f_i = fresnel_dielectric(wiz, pr[6], pr[7]);
+    const float ssw = pr[10];
+    float p_spec = f_i * ssw;
+    const float p_diff0 = (1.f - f_i) * (1.f - ssw);
+    p_spec = p_spec / (p_spec + p_diff0);
+    const float p_diff = 1.f - p_spec;
+    const bool spec = wiz > 0.f && u_lobe < p_spec;
+    if (spec) reflect_mixed(n, wix, wiy, wiz, wo);
+    const float pdf = fmaxf(spec ? p_spec : p_diff * (wo[2] / (float)M_PI), 1e-10f);
+    const float f_o = fresnel_dielectric(wo[2], pr[6], pr[7]);
+    for (int q = 0; q < 3; ++q)
+      f[q] = spec ? pr[3 + q] * (f_i / pdf)
+                  : pr[q] / pr[8] * pdf * pr[9] * (1.f - f_i) * (1.f - f_o);
+  }
+  // Phong and Plastic leave wo as drawn; BSDFSample.compose normalizes the selected one (:56)
+  if (c.kind != NRT_BSDF_DIFFUSE) normalize3(wo[0], wo[1], wo[2], 1e-12f);
+}
+
 // One wave shades 32 hit rays.  The MLP evaluations of the light, the spatial weights and each
 // NeuralBSDF run through ONE call site (a job loop) so every hidden width is inlined once.
-template <bool F16>
+// EXT: the mixture has a Phong, Plastic or two-sided component, or the call is nrt_bsdf_eval
+// (ls_in / pdf_out); without it the kernel is the NeuralBSDF / Diffuse / Conductor shader alone,
+// which keeps that instantiation's registers (DESIGN.md "Analytic BSDF models")
+template <bool F16, bool EXT>
 __global__ void __launch_bounds__(256) k_shade_direct(
     const BsdfDev* __restrict__ bp, const LightDev* __restrict__ lp, const float* __restrict__ P_,
     const float* __restrict__ N_, const float* __restrict__ WI, const int32_t* __restrict__ hit_idx,
     const int32_t* __restrict__ hit_count, const float* __restrict__ lscale,
-    float* __restrict__ rgb, float* __restrict__ wout, int RS, int per_wave) {
+    float* __restrict__ rgb, float* __restrict__ wout, int RS, int per_wave,
+    const float* __restrict__ ls_in, float* __restrict__ pdf_out) {
   extern __shared__ float smem[];
   const BsdfDev& bs = *bp;
-  const LightDev& lt = *lp;
+  // ls_in (nrt_bsdf_eval): the LS record of each listed ray stands in for the light (lp unused)
+  const int lkind = (EXT && ls_in) ? -1 : lp->kind;
   WaveLds l = wave_lds(smem, per_wave, RS, F16);
   // per-wave scratch after Y: spatial weights K[32][kMaxComponents]
   float* Kw = l.Y + 32 * 32;
@@ -1497,31 +1636,45 @@ __global__ void __launch_bounds__(256) k_shade_direct(
 
     float ldx = 0.f, ldy = 0.f, ldz = 0.f, le[3] = {0.f, 0.f, 0.f}, wo[3] = {0.f, 0.f, 0.f};
     float feat[3] = {0.f, 0.f, 0.f};
-    float f[3] = {0.f, 0.f, 0.f};
-    if (lt.kind == 1) {
+    float f[3] = {0.f, 0.f, 0.f}, pd = 0.f;
+    if (lkind == 1) {
       // PointLights.sample_direction (lights.py:89-110 / renderer/lighting.py:283-304)
       float dist;
-      point_light(lt, px, py, pz, ldx, ldy, ldz, le, dist);
+      point_light(*lp, px, py, pz, ldx, ldy, ldz, le, dist);
       to_local(fr, ldx, ldy, ldz, wo);
       rusin2(wix, wiy, wiz, wo[0], wo[1], wo[2], feat);
+    } else if (EXT && lkind < 0) {
+      const float* q = ls_in + (valid ? i : total - 1) * kLsStride;
+      le[0] = q[0]; le[1] = q[1]; le[2] = q[2];
+      feat[0] = q[3]; feat[1] = q[4]; feat[2] = q[5];
+      wo[0] = q[6]; wo[1] = q[7]; wo[2] = q[8];
     }
     if (!bs.spatial)
       for (int j = lane >> 5; j < nc; j += 2) Kw[r * kMaxComponents + j] = 1.f;
     // job list: -2 light field, -1 spatial weights, 0..nc-1 components
     for (int job = -2; job < nc; ++job) {
       const MlpDev* m = nullptr;
-      if (job == -2) m = (lt.kind == 0) ? lt.mlp : nullptr;
+      if (job == -2) m = (lkind == 0) ? lp->mlp : nullptr;
       else if (job == -1) m = bs.spatial;
       else m = (bs.comp[job].kind == 0) ? bs.comp[job].mlp : nullptr;
       if (m) {
         EncIn e;
         e.xg = nullptr; e.lat = nullptr; e.x[3] = 0.f;
         if (job < 0) { e.x[0] = px; e.x[1] = py; e.x[2] = pz; }
-        else { e.x[0] = feat[0]; e.x[1] = feat[1]; e.x[2] = feat[2]; }
+        else {
+          e.x[0] = feat[0]; e.x[1] = feat[1]; e.x[2] = feat[2];
+          if (EXT && bs.comp[job].two_sided && wiz < 0.f) {
+            // Bidirectional(NeuralBSDF): the back side reads param_rusin2 of the z-inverted pair
+            float fb[3];
+            rusin2(wix, wiy, -wiz, wo[0], wo[1], -wo[2], fb);
+            e.x[0] = fb[0]; e.x[1] = fb[1]; e.x[2] = fb[2];
+          }
+        }
         mlp_eval_any<F16>(*m, e, l.X, RS, l.Y, ys);
       }
       if (job == -2) {
-        if (lt.kind == 0) {
+        if (lkind == 0) {
+          const LightDev& lt = *lp;
           // LightField.sample_direction (lights.py:175-195)
           float vx = l.Y[r * ys], vy = l.Y[r * ys + 1], vz = l.Y[r * ys + 2];
           float mag = sqrtf(vx * vx + vy * vy + vz * vz);
@@ -1539,25 +1692,24 @@ __global__ void __launch_bounds__(256) k_shade_direct(
           for (int j = lane >> 5; j < nc; j += 2) Kw[r * kMaxComponents + j] = sigmoidf_(l.Y[r * ys + j]);
       } else {
         const BsdfCompDev& c = bs.comp[job];
-        float v[3];
+        float v[3], pj = 1.f;
         if (c.kind == 0) {
-          for (int q = 0; q < 3; ++q) v[q] = act_fwd<false>(l.Y[r * ys + q], c.act);
-        } else if (c.kind == 1) {
-          // Diffuse.eval_and_pdf (bsdfs.py:108-118)
-          for (int q = 0; q < 3; ++q) {
-            float x = wo[2] * c.params[q];
-            v[q] = (c.act == ACT_NONE) ? x / (float)M_PI : act_fwd<false>(x, c.act);
-          }
+          // NeuralBSDF.eval_and_pdf (bsdfs.py:634-637): pdf 1; two-sided: zero at wi.z == 0
+          const bool off = EXT && c.two_sided && wiz == 0.f;
+          for (int q = 0; q < 3; ++q) v[q] = off ? 0.f : act_fwd<false>(l.Y[r * ys + q], c.act);
+          if (off) pj = 0.f;
         } else {
-          // Conductor.eval_and_pdf (bsdfs.py:364-388)
-          float rx = -wix, ry = -wiy, rz = wiz;
-          bool th = ((rx * wo[0] + ry * wo[1]) + rz * wo[2]) > 0.94f;
-          float fres = fresnel_conductor(wiz, c.params[3]);
-          for (int q = 0; q < 3; ++q) v[q] = th ? fres * act_fwd<false>(c.params[q], c.act) : 0.f;
+          const float nrm[3] = {fr[2], fr[5], fr[8]};
+          if (EXT)
+            bsdf_comp_eval(c, nrm, wix, wiy, wiz, wo[0], wo[1], wo[2], v, pj);
+          else
+            bsdf_model_eval(c.kind == NRT_BSDF_DIFFUSE ? NRT_BSDF_DIFFUSE : NRT_BSDF_CONDUCTOR, c.act,
+                            c.params, nrm, wix, wiy, wiz, wo[0], wo[1], wo[2], v, pj);
         }
         wave_lds_fence();
         const float kj = Kw[r * kMaxComponents + job];
         f[0] += v[0] * kj; f[1] += v[1] * kj; f[2] += v[2] * kj;
+        if (EXT) pd += pj * kj;
       }
       wave_lds_fence();
     }
@@ -1570,6 +1722,7 @@ __global__ void __launch_bounds__(256) k_shade_direct(
       rgb[idx * 3] = (1.f * f[0]) * le[0];
       rgb[idx * 3 + 1] = (1.f * f[1]) * le[1];
       rgb[idx * 3 + 2] = (1.f * f[2]) * le[2];
+      if (EXT && pdf_out) pdf_out[idx] = pd;
       if (wout)
         for (int j = 0; j < nc; ++j) wout[idx * nc + j] = Kw[r * kMaxComponents + j];
     }
@@ -1580,9 +1733,9 @@ __global__ void __launch_bounds__(256) k_shade_direct(
 // ------------------------------------------------------------------------------------------
 // FP16 shading on the program engine: k_light16 (emitter sample per hit) then k_bsdf16
 // (spatial weights + components).  Same math as k_shade_direct; LS carries, per position i of
-// the hit list, le (3) | feat = param_rusin2(wi, wo) (3) | wo (3) | pad (3).
+// the hit list, le (3) | feat = param_rusin2(wi, wo) (3) | wo (3) | the features of the z-inverted
+// pair for a two-sided NeuralBSDF (3; k_ls_flip / k_eval_prep, unwritten otherwise).
 // ------------------------------------------------------------------------------------------
-constexpr int kLsStride = 12;
 
 __device__ __forceinline__ void light_from_field(float vx, float vy, float vz, const LightDev& lt,
                                                  const float fr[9], float wix, float wiy,
@@ -1598,6 +1751,57 @@ __device__ __forceinline__ void light_from_field(float vx, float vy, float vz, c
   le[0] = mag * lt.color_sig[0]; le[1] = mag * lt.color_sig[1]; le[2] = mag * lt.color_sig[2];
   to_local(fr, ldx, ldy, ldz, wo);
   rusin2(wix, wiy, wiz, wo[0], wo[1], wo[2], feat);
+}
+
+// LS[9..11] = param_rusin2 of the z-inverted pair (invert_z(wi), invert_z(wo)), the input of a
+// two-sided NeuralBSDF's back side (bsdfs.py:442-444); runs after the light stage, and only for a
+// mixture that has such a component
+template <int = 0>
+__global__ void k_ls_flip(const float* __restrict__ WI, const int32_t* __restrict__ hit_idx,
+                          const int32_t* __restrict__ hit_count, float* __restrict__ LS) {
+  const int64_t total = *hit_count;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t idx = hit_idx[i];
+    float* o = LS + i * kLsStride;
+    float fb[3];
+    rusin2(WI[idx * 3], WI[idx * 3 + 1], -WI[idx * 3 + 2], o[6], o[7], -o[8], fb);
+    o[9] = fb[0]; o[10] = fb[1]; o[11] = fb[2];
+  }
+}
+
+// nrt_bsdf_eval: the LS record of a caller-supplied wo in place of the light stage -- le = 1,
+// feat = param_rusin2(wi, wo), wo, and the flipped features when the mixture needs them
+template <int = 0>
+__global__ void k_eval_prep(const float* __restrict__ WI, const float* __restrict__ WO,
+                            const int32_t* __restrict__ hit_idx,
+                            const int32_t* __restrict__ hit_count, int flip, float* __restrict__ LS) {
+  const int64_t total = *hit_count;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t idx = hit_idx[i];
+    const float wix = WI[idx * 3], wiy = WI[idx * 3 + 1], wiz = WI[idx * 3 + 2];
+    const float w0 = WO[idx * 3], w1 = WO[idx * 3 + 1], w2 = WO[idx * 3 + 2];
+    float* o = LS + i * kLsStride;
+    float ft[3];
+    rusin2(wix, wiy, wiz, w0, w1, w2, ft);
+    o[0] = 1.f; o[1] = 1.f; o[2] = 1.f;
+    o[3] = ft[0]; o[4] = ft[1]; o[5] = ft[2];
+    o[6] = w0; o[7] = w1; o[8] = w2;
+    if (flip) {
+      rusin2(wix, wiy, -wiz, w0, w1, -w2, ft);
+      o[9] = ft[0]; o[10] = ft[1]; o[11] = ft[2];
+    }
+  }
+}
+
+// every ray listed, in order (nrt_bsdf_eval without an active mask)
+template <int = 0>
+__global__ void k_all_list(int64_t P, int32_t* __restrict__ idx, int32_t* __restrict__ cnt) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P;
+       i += (int64_t)gridDim.x * blockDim.x)
+    idx[i] = (int32_t)i;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *cnt = (int32_t)P;
 }
 
 // FIELD: LightField MLP (8 x 32 hidden blocks, F = 16) on the ring; else a point light (VALU only)
@@ -1655,7 +1859,7 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf16(
     const ProgDev prog, const BsdfDev* __restrict__ bp, const float* __restrict__ P_,
     const float* __restrict__ WI, const int32_t* __restrict__ hit_idx,
     const int32_t* __restrict__ hit_count, const float* __restrict__ LS, float* __restrict__ rgb,
-    float* __restrict__ wout) {
+    float* __restrict__ wout, const float* __restrict__ N_, float* __restrict__ pdf_out) {
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   const BsdfDev& bs = *bp;
   const int nc = bs.n;
@@ -1692,33 +1896,35 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf16(
       for (int j = lane >> 5; j < nc; j += 2) Kw[r * kMaxComponents + j] = 1.f;
     }
     wave_lds_fence();
-    float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+    float f0 = 0.f, f1 = 0.f, f2 = 0.f, pd = 0.f;
     for (int j = 0; j < nc; ++j) {
       const BsdfCompDev& c = bs.comp[j];
-      float v[3];
+      float v[3], pj = 1.f;
       if (c.kind == 0) {
-        const f16v o = ring::keval<3, 9, WV, ACT_LEAKY>(E, prog.mlp[k], ft0, ft1, ft2);
+        float x0 = ft0, x1 = ft1, x2 = ft2;
+        float wiz = 1.f;
+        if (c.two_sided) {  // Bidirectional(NeuralBSDF): the flipped features where wi.z < 0
+          wiz = WI[idx * 3 + 2];
+          if (wiz < 0.f) { x0 = ls[9]; x1 = ls[10]; x2 = ls[11]; }
+        }
+        const f16v o = ring::keval<3, 9, WV, ACT_LEAKY>(E, prog.mlp[k], x0, x1, x2);
         ++k;
 #pragma unroll
-        for (int q = 0; q < 3; ++q) v[q] = act_fwd<false>(ring::tile_row(o, q, lane), c.act);
-      } else if (c.kind == 1) {
-        // Diffuse.eval_and_pdf (bsdfs.py:108-118)
-        for (int q = 0; q < 3; ++q) {
-          float x = wo2 * c.params[q];
-          v[q] = (c.act == ACT_NONE) ? x / (float)M_PI : act_fwd<false>(x, c.act);
-        }
+        for (int q = 0; q < 3; ++q)
+          v[q] = wiz == 0.f ? 0.f : act_fwd<false>(ring::tile_row(o, q, lane), c.act);
+        if (wiz == 0.f) pj = 0.f;
       } else {
-        // Conductor.eval_and_pdf (bsdfs.py:364-388)
         const float wix = WI[idx * 3], wiy = WI[idx * 3 + 1], wiz = WI[idx * 3 + 2];
-        float rx = -wix, ry = -wiy, rz = wiz;
-        bool th = ((rx * wo0 + ry * wo1) + rz * wo2) > 0.94f;
-        float fres = fresnel_conductor(wiz, c.params[3]);
-        for (int q = 0; q < 3; ++q) v[q] = th ? fres * act_fwd<false>(c.params[q], c.act) : 0.f;
+        float nw[3] = {N_[idx * 3], N_[idx * 3 + 1], N_[idx * 3 + 2]};
+        normalize3(nw[0], nw[1], nw[2], 1e-7f);  // it.frame[..., 2] (make_frame)
+        bsdf_comp_eval(c, nw, wix, wiy, wiz, wo0, wo1, wo2, v, pj);
       }
       const float kj = Kw[r * kMaxComponents + j];
       f0 += v[0] * kj; f1 += v[1] * kj; f2 += v[2] * kj;
+      pd += pj * kj;
     }
     if (valid && lane < 32) {
+      if (pdf_out) pdf_out[idx] = pd;
       // integrators.py:186-189: mis(=1) * bsdf_val * emitter_val, / emitter_samples(=1)
       rgb[idx * 3] = (1.f * f0) * le0;
       rgb[idx * 3 + 1] = (1.f * f1) * le1;

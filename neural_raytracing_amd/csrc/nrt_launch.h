@@ -288,7 +288,12 @@ int build_light_program(nrt_light* l);
 int build_bsdf_program(nrt_bsdf* b);
 int shade_program(const nrt_bsdf* b, const nrt_light* l, const float* p, const float* n,
                   const float* wi, const int32_t* hit_idx, const int32_t* hit_count, int64_t P,
-                  const float* lscale, float* rgb, float* weights_out, hipStream_t st);
+                  const float* lscale, float* rgb, float* weights_out, hipStream_t st,
+                  const float* ls_in = nullptr, float* pdf_out = nullptr);
+// ls_in (nrt_bsdf_eval): a ready LS record per listed ray replaces the light stage (l unused);
+// pdf_out [P] (optional): sum_j k_j pdf_j
+int ls_flip(const nrt_bsdf* b, const float* wi, const int32_t* hit_idx, const int32_t* hit_count,
+            int64_t P, float* ls, hipStream_t st);
 
 // ---- FP32 / fp32-split shading on the row-program ring engines (nrt_shade_ring.hip) ----
 int build_rprog(const std::vector<const nrt_mlp*>& mlps, bool split, nrt_rprog& out, int mode = 0);
@@ -321,7 +326,8 @@ bool solo_refresh_maps(const nrt_mlp* m, std::vector<int>& stream_map, std::vect
                        void*& stream_dst, void*& bias_dst);
 int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const float* n,
                const float* wi, const int32_t* hit_idx, const int32_t* hit_count, int64_t P,
-               const float* lscale, float* rgb, float* weights_out, int precision, hipStream_t st);
+               const float* lscale, float* rgb, float* weights_out, int precision, hipStream_t st,
+               const float* ls_in = nullptr, float* pdf_out = nullptr);
 // ---- the MLP backward on the ring engine (nrt_train_ring.h, launched from nrt_shade_ring.hip) --
 // the bytes of the device job table ring_backward needs for n MLPs
 size_t ring_backward_table_bytes(int n);

@@ -124,15 +124,16 @@ int persistent_blocks(K kern, int threads, size_t lds, int64_t want) {
 // NRT_EUNSUPPORTED when the program path does not cover this light / BSDF pair
 int shade_program(const nrt_bsdf* b, const nrt_light* l, const float* p, const float* n,
                   const float* wi, const int32_t* hit_idx, const int32_t* hit_count, int64_t P,
-                  const float* lscale, float* rgb, float* weights_out, hipStream_t st) {
-  const bool field = l->host_dev.kind == 0;
+                  const float* lscale, float* rgb, float* weights_out, hipStream_t st,
+                  const float* ls_in, float* pdf_out) {
+  const bool field = !ls_in && l->host_dev.kind == 0;
   if ((field && !l->prog.ok) || !b->prog.ok) return NRT_EUNSUPPORTED;
   constexpr int WV = kShadeWaves;
-  float* ls = nullptr;
-  NRT_HIP(hipMallocAsync((void**)&ls, (size_t)P * kLsStride * sizeof(float), st));
+  float* ls = const_cast<float*>(ls_in);
+  if (!ls_in) NRT_HIP(hipMallocAsync((void**)&ls, (size_t)P * kLsStride * sizeof(float), st));
   const int64_t want = ceil_div64(P, 32 * WV);
   int rc = NRT_OK;
-  {
+  if (!ls_in) {
     ProfScope prof("k_light16", st);
     if (field) {
       auto kern = k_light16<WV, true>;
@@ -149,20 +150,31 @@ int shade_program(const nrt_bsdf* b, const nrt_light* l, const float* p, const f
       rc = check_launch("k_light16");
     }
   }
+  if (!rc && !ls_in) rc = ls_flip(b, wi, hit_idx, hit_count, P, ls, st);
   if (!rc) {
     ProfScope prof("k_bsdf16", st);
     const size_t lds = ring::KEngine<WV>::lds_bytes(b->prog.d) + (size_t)WV * 32 * kMaxComponents * 4;
     auto launch = [&](auto kern) {
       if ((rc = set_lds(kern, lds))) return;
       kern<<<dim3(persistent_blocks(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
-          b->prog.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out);
+          b->prog.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out, n, pdf_out);
       rc = check_launch("k_bsdf16");
     };
     if (b->spatial) launch(k_bsdf16<WV, true>);
     else launch(k_bsdf16<WV, false>);
   }
-  (void)hipFreeAsync(ls, st);
+  if (!ls_in) (void)hipFreeAsync(ls, st);
   return rc;
+}
+
+// the flipped features of a mixture with a two-sided NeuralBSDF, after any light stage
+int ls_flip(const nrt_bsdf* b, const float* wi, const int32_t* hit_idx, const int32_t* hit_count,
+            int64_t P, float* ls, hipStream_t st) {
+  if (!b->host_dev.flip_feat) return NRT_OK;
+  ProfScope prof("k_ls_flip", st);
+  k_ls_flip<><<<dim3(std::max<int64_t>(1, std::min<int64_t>(ceil_div64(P, 256), 1024))), dim3(256), 0, st>>>(
+      wi, hit_idx, hit_count, ls);
+  return check_launch("k_ls_flip");
 }
 
 }  // namespace nrt

@@ -566,7 +566,7 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf_r(
     const RProgDev prog, const BsdfDev* __restrict__ bp, const float* __restrict__ P_,
     const float* __restrict__ WI, const int32_t* __restrict__ hit_idx,
     const int32_t* __restrict__ hit_count, const float* __restrict__ LS, float* __restrict__ rgb,
-    float* __restrict__ wout) {
+    float* __restrict__ wout, const float* __restrict__ N_, float* __restrict__ pdf_out) {
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   const BsdfDev& bs = *bp;
   const int nc = bs.n;
@@ -586,7 +586,7 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf_r(
     const float ft0 = ls[3], ft1 = ls[4], ft2 = ls[5];
     const float wo0 = ls[6], wo1 = ls[7], wo2 = ls[8];
     float K[16];
-    float f0, f1, f2;
+    float f0, f1, f2, pd;
     // the tile's evaluations; the split path repeats them while the range guard asks
     for (;;) {
     bool ok = true;
@@ -602,34 +602,34 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf_r(
 #pragma unroll
       for (int q = 0; q < 16; ++q) K[q] = 1.f;
     }
-    f0 = 0.f; f1 = 0.f; f2 = 0.f;
+    f0 = 0.f; f1 = 0.f; f2 = 0.f; pd = 0.f;
     for (int c = 0; c < nc; ++c) {
       const BsdfCompDev& cp = bs.comp[c];
-      float v[3];
+      float v[3], pj = 1.f;
       if (cp.kind == 0) {
-        const f4v o = eval<PREC, BsdfShape, ACT_LEAKY>(E, prog.mlp[k], k, ft0, ft1, ft2);
+        float x0 = ft0, x1 = ft1, x2 = ft2;
+        float wiz = 1.f;
+        if (cp.two_sided) {  // Bidirectional(NeuralBSDF): the flipped features where wi.z < 0
+          wiz = WI[idx * 3 + 2];
+          if (wiz < 0.f) { x0 = ls[9]; x1 = ls[10]; x2 = ls[11]; }
+        }
+        const f4v o = eval<PREC, BsdfShape, ACT_LEAKY>(E, prog.mlp[k], k, x0, x1, x2);
         ok = ok && finite4(o);
         ++k;
 #pragma unroll
-        for (int q = 0; q < 3; ++q) v[q] = act_fwd<false>(out_row(o, q, lane), cp.act);
-      } else if (cp.kind == 1) {
-        // Diffuse.eval_and_pdf (bsdfs.py:108-118)
-        for (int q = 0; q < 3; ++q) {
-          float x = wo2 * cp.params[q];
-          v[q] = (cp.act == ACT_NONE) ? x / (float)M_PI : act_fwd<false>(x, cp.act);
-        }
+        for (int q = 0; q < 3; ++q) v[q] = wiz == 0.f ? 0.f : act_fwd<false>(out_row(o, q, lane), cp.act);
+        if (wiz == 0.f) pj = 0.f;
       } else {
-        // Conductor.eval_and_pdf (bsdfs.py:364-388)
         const float wix = WI[idx * 3], wiy = WI[idx * 3 + 1], wiz = WI[idx * 3 + 2];
-        float rx = -wix, ry = -wiy, rz = wiz;
-        bool th = ((rx * wo0 + ry * wo1) + rz * wo2) > 0.94f;
-        float fres = fresnel_conductor(wiz, cp.params[3]);
-        for (int q = 0; q < 3; ++q) v[q] = th ? fres * act_fwd<false>(cp.params[q], cp.act) : 0.f;
+        float nw[3] = {N_[idx * 3], N_[idx * 3 + 1], N_[idx * 3 + 2]};
+        normalize3(nw[0], nw[1], nw[2], 1e-7f);  // it.frame[..., 2] (make_frame)
+        bsdf_comp_eval(cp, nw, wix, wiy, wiz, wo0, wo1, wo2, v, pj);
       }
       float kj = K[0];
 #pragma unroll
       for (int q = 1; q < 16; ++q) kj = c == q ? K[q] : kj;
       f0 += v[0] * kj; f1 += v[1] * kj; f2 += v[2] * kj;
+      pd += pj * kj;
     }
     if (PREC != 2 || !E.retry(ok)) break;
     }
@@ -638,6 +638,7 @@ __global__ void __launch_bounds__(64 * WV, 1) k_bsdf_r(
       rgb[idx * 3] = (1.f * f0) * le0;
       rgb[idx * 3 + 1] = (1.f * f1) * le1;
       rgb[idx * 3 + 2] = (1.f * f2) * le2;
+      if (pdf_out) pdf_out[idx] = pd;
       if (wout)
 #pragma unroll
         for (int q = 0; q < 16; ++q)

@@ -381,13 +381,15 @@ int with_depth_occ(const RProgDev& d, KF&& kern_of, F&& f) {
 // NRT_EUNSUPPORTED when the row-program kernels do not cover this light / BSDF pair
 int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const float* n,
                const float* wi, const int32_t* hit_idx, const int32_t* hit_count, int64_t P,
-               const float* lscale, float* rgb, float* weights_out, int precision, hipStream_t st) {
+               const float* lscale, float* rgb, float* weights_out, int precision, hipStream_t st,
+               const float* ls_in, float* pdf_out) {
   const bool split = precision == NRT_FP32_SPLIT || precision == NRT_MIXED;  // NRT_MIXED shades at fp32-split
   const int pi = split ? 1 : 0;
-  const bool field = l->host_dev.kind == 0;
+  const bool field = !ls_in && l->host_dev.kind == 0;
   if (b->host_dev.n > 16) return NRT_EUNSUPPORTED;
   // build on first use
-  nrt_rprog& lp = l->rprog[pi];
+  nrt_rprog none;
+  nrt_rprog& lp = ls_in ? none : l->rprog[pi];
   nrt_rprog& bp = b->rprog[pi];
   if (field && !lp.built) {
     if (l->mlp && shape_ok(l->mlp, kLightSpec) && l->mlp->desc.out == 3) {
@@ -413,12 +415,13 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
   }
   if ((field && !lp.ok) || !bp.ok) return NRT_EUNSUPPORTED;
   constexpr int WV = kRWaves;
-  float* ls = nullptr;
-  NRT_HIP(hipMallocAsync((void**)&ls, (size_t)std::max<int64_t>(P, 1) * kLsStride * sizeof(float), st));
+  float* ls = const_cast<float*>(ls_in);
+  if (!ls_in)
+    NRT_HIP(hipMallocAsync((void**)&ls, (size_t)std::max<int64_t>(P, 1) * kLsStride * sizeof(float), st));
   const int64_t want = ceil_div64(P, 16 * WV);
   int rc = NRT_OK;
   auto run = [&]<int PREC>() -> int {
-    {
+    if (!ls_in) {
       ProfScope prof(PREC == 2 ? "k_light3" : "k_light32", st);
       if (field) {
         rc = with_depth<PREC, WV>(lp.d, [&](auto dd) -> int {
@@ -437,6 +440,7 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
         rc = check_launch("k_light16");
       }
     }
+    if (!rc && !ls_in) rc = ls_flip(b, wi, hit_idx, hit_count, P, ls, st);
     if (rc) return rc;
     ProfScope prof(PREC == 2 ? "k_bsdf3" : "k_bsdf32", st);
     return with_depth<PREC, WV>(bp.d, [&](auto dd) -> int {
@@ -445,7 +449,7 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
       auto launch = [&](auto kern) -> int {
         if (int r = set_lds(kern, lds)) return r;
         kern<<<dim3(persistent_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
-            bp.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out);
+            bp.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out, n, pdf_out);
         return check_launch("k_bsdf_r");
       };
       return b->spatial ? launch(rprog::k_bsdf_r<PREC, D, WV, true>)
@@ -453,7 +457,7 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
     });
   };
   rc = split ? run.template operator()<2>() : run.template operator()<0>();
-  (void)hipFreeAsync(ls, st);
+  if (!ls_in) (void)hipFreeAsync(ls, st);
   return rc;
 }
 

@@ -1,5 +1,7 @@
 """BSDFs on the hot path (bsdf/bsdfs.py).  ``ComposeSpatialVarying`` of ``NeuralBSDF`` /
-``Diffuse`` / ``Conductor`` evaluates inside the fused shading kernel ``nrt_shade_direct``."""
+``Diffuse`` / ``Conductor`` / ``Phong`` / ``Plastic`` components, each optionally wrapped in
+``Bidirectional``, evaluates inside the fused shading kernel ``nrt_shade_direct``; ``eval_and_pdf``
+of every class is the same BSDF stage at a caller-supplied ``wo`` (``nrt_bsdf_eval``)."""
 import ctypes
 import math
 
@@ -31,6 +33,54 @@ class BSDF(nn.Module):
 
     def eval_and_pdf(self, it, wo, active=True):
         raise NotImplementedError()
+
+    # which outputs eval_and_pdf zeroes where ~active, per class as the reference does
+    _mask_spectrum = False
+    _mask_pdf = False
+
+    def _eval_hip(self, it, wo, active):
+        """eval_and_pdf on the HIP path: nrt_bsdf_eval without gradients, differentiable.bsdf_eval
+        when a parameter or an input requires one.  `it`: anything with p, n, wi."""
+        from ..differentiable import bsdf_eval, needs_grad
+        lead = it.p.shape[:-1]
+        if not torch.is_tensor(active):
+            active = torch.full(lead, bool(active), dtype=torch.bool, device=it.p.device)
+        active = active.expand(lead)
+        if needs_grad(self) or (torch.is_grad_enabled() and
+                                any(t.requires_grad for t in (it.p, it.wi, wo))):
+            return bsdf_eval(self, it, wo, active)
+        from ..integrators.integrators import _bsdf_handle
+        dev = it.p.device
+        names = ("it.p", "it.n", "it.wi", "wo", "active")
+        for name, t in zip(names, (it.p, it.n, it.wi, wo, active)):
+            # the library reads raw device pointers: nothing from the host or another GPU
+            if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+                raise _lib.NrtError(f"eval_and_pdf: {name} must be a tensor on the GPU of it.p "
+                                    f"(got {getattr(t, 'device', type(t).__name__)}, it.p on {dev})")
+        P = active.numel()
+        flat = [t.detach().expand(lead + (3,)).reshape(P, 3).float().contiguous()
+                for t in (it.p, it.n, it.wi, wo)]
+        spectrum = torch.empty(P, 3, device=dev)
+        pdf = torch.empty(P, device=dev)
+        both = self._mask_spectrum and self._mask_pdf
+        # a mixture with a weights MLP evaluates every ray and masks afterwards, so that the one
+        # evaluation of the MLP also gives it.normalized_weights on every ray (bsdfs.py:516-520)
+        weights = None
+        if getattr(self, "sp_var_fn", None) is not None:
+            weights = torch.empty(P, len(self.bsdfs), device=dev)
+        act = active.reshape(P).to(torch.uint8).contiguous() if both and weights is None else None
+        _lib.call("nrt_bsdf_eval", _bsdf_handle(self), *[_lib.ptr(t) for t in flat], _lib.ptr(act),
+                  P, _lib.ptr(spectrum), _lib.ptr(pdf), _lib.ptr(weights), _lib.precision_code(),
+                  _lib.stream())
+        spectrum = spectrum.reshape(lead + (3,))
+        pdf = pdf.reshape(lead)
+        if self._mask_spectrum and act is None:
+            spectrum = torch.where(active.unsqueeze(-1), spectrum, torch.zeros_like(spectrum))
+        if self._mask_pdf and act is None:
+            pdf = torch.where(active, pdf, torch.zeros_like(pdf))
+        if weights is not None:
+            setattr(it, "normalized_weights", weights.reshape(lead + (len(self.bsdfs),)))
+        return spectrum, pdf
 
     def joint_eval_pdf(self, it, wo, active=True):
         spectrum, pdf = self.eval_and_pdf(it, wo, active)
@@ -69,6 +119,10 @@ class Diffuse(BSDF):
         refl = self.reflectance.detach().float().cpu().tolist()
         return (_lib.NRT_BSDF_DIFFUSE, None, act, refl + [0.0])
 
+    def eval_and_pdf(self, it, wo, active=True):
+        """bsdfs.py:108-118 (not masked)."""
+        return self._eval_hip(it, wo, active)
+
 
 class Conductor(BSDF):
     """Conductor (bsdfs.py:345-388)."""
@@ -96,6 +150,12 @@ class Conductor(BSDF):
         spec = self.specular.detach().float().cpu().tolist()
         return (_lib.NRT_BSDF_CONDUCTOR, None, _lib.ACT[activation_code(self.act)], spec + [eta])
 
+    _mask_spectrum = True
+
+    def eval_and_pdf(self, it, wo, active=True):
+        """bsdfs.py:364-388 (the spectrum is masked, the pdf is not)."""
+        return self._eval_hip(it, wo, active)
+
 
 class NeuralBSDF(BSDF):
     """act(SkipConnMLP_6x96,F=64(param_rusin2(it.wi, wo))), pdf 1 (bsdfs.py:613-637)."""
@@ -117,8 +177,8 @@ class NeuralBSDF(BSDF):
                 [0.0, 0.0, 0.0, 0.0])
 
     def eval_and_pdf(self, it, wo, active=True):
-        raise _lib.NrtError("NeuralBSDF evaluates inside Direct.sample's fused shading kernel "
-                            "(nrt_shade_direct)")
+        """bsdfs.py:634-637 (not masked)."""
+        return self._eval_hip(it, wo, active)
 
 
 class ComposeSpatialVarying(BSDF):
@@ -148,29 +208,42 @@ class ComposeSpatialVarying(BSDF):
         if sp is not None and sph is None:
             raise _lib.NrtError("spatial_varying_fn must be a SkipConnMLP on the HIP path")
         def build():
-            arr = (_lib.BsdfComponent * len(comps))()
-            for i, (kind, mh, act, params) in enumerate(comps):
+            arr = (_lib.BsdfComponentEx * len(comps))()
+            for i, comp in enumerate(comps):
+                kind, mh, act, params = comp[:4]
+                back = comp[4] if len(comp) > 4 else None
                 arr[i].kind = kind
                 arr[i].mlp = mh.value if mh is not None else None
                 arr[i].activation = act
-                for q in range(4):
-                    arr[i].params[q] = float(params[q])
+                for q, v in enumerate(params):
+                    arr[i].params[q] = float(v)
+                if back is not None:  # Bidirectional: (kind, activation, params) of the back side
+                    arr[i].two_sided = 1
+                    arr[i].back_kind, arr[i].back_activation = back[0], back[1]
+                    for q, v in enumerate(back[2]):
+                        arr[i].back_params[q] = float(v)
             out = ctypes.c_void_p()
-            _lib.check(_lib.load().nrt_bsdf_create(len(comps), arr, sph.value if sph else None,
-                                                   ctypes.byref(out)), "nrt_bsdf_create")
+            _lib.check(_lib.load().nrt_bsdf_create_ex(len(comps), arr, sph.value if sph else None,
+                                                      ctypes.byref(out)), "nrt_bsdf_create_ex")
             deps = [c[1] for c in comps if c[1] is not None] + ([sph] if sph else [])
             return _Handle(out, "nrt_bsdf_destroy", deps)
 
         cached = getattr(self, "_nrt_bsdf", None)
-        key = tuple((c[0], c[2], tuple(c[3]), id(c[1])) for c in comps) + (id(sph),)
+        key = tuple((c[0], c[2], tuple(c[3]), id(c[1]),
+                     (c[4][0], c[4][1], tuple(c[4][2])) if len(c) > 4 and c[4] else None)
+                    for c in comps) + (id(sph),)
         if cached is None or cached[0] != key:
             object.__setattr__(self, "_nrt_bsdf", (key, build()))
         return self._nrt_bsdf[1].value
 
+    _mask_spectrum = True
+    _mask_pdf = True
+
     def eval_and_pdf(self, it, wo, active=True):
-        raise _lib.NrtError("ComposeSpatialVarying evaluates inside Direct.sample's fused "
-                            "shading kernel (nrt_shade_direct); standalone eval_and_pdf is not "
-                            "on the HIP path yet")
+        """bsdfs.py:515-528: sum_j k_j [f_j | pdf_j], zero where ~active; sets
+        it.normalized_weights on every ray, as the reference does (from the kernel's weights
+        output; with gradients, differentiable.bsdf_eval sets it with its graph)."""
+        return self._eval_hip(it, wo, active)
 
     def normalized_weights(self, p, it):
         w = self.sp_var_fn(self.preprocess(p)).reshape(p.shape[:-1] + (len(self.bsdfs),))
@@ -178,26 +251,14 @@ class ComposeSpatialVarying(BSDF):
         return w.sigmoid()
 
 
-# ---- reference BSDFs outside the hot path (import surface of scripts/*.py) ----------------------
-# The drivers import Phong, Plastic and Bidirectional (nerf_synthetic.py:10-12, dtu.py:11-13,
-# colocate.py:10-12) without rendering them.  Their constructors and parameters() follow
-# bsdfs.py:132-149, 238-270 and the Bidirectional wrapper; shading with them is not on the HIP path
-# and raises NrtError, as any unrecognised BSDF does.
+# ---- the analytic models: Phong, Plastic and the two-sided wrapper ------------------------------
 
-class _Unsupported(BSDF):
-    def _component(self):
-        raise _lib.NrtError(f"BSDF {type(self).__name__} has no HIP implementation (supported: "
-                            "NeuralBSDF, Diffuse, Conductor, ComposeSpatialVarying)")
-
-    def eval_and_pdf(self, it, wo, active=True):
-        self._component()
-
-    def sample(self, it, sampler, active=True):
-        self._component()
+def _pad(params):
+    return list(params) + [0.0] * (_lib.NRT_BSDF_PARAMS - len(params))
 
 
-class Phong(_Unsupported):
-    """bsdfs.py:132-189 (constructor, parameters, random)."""
+class Phong(BSDF):
+    """bsdfs.py:132-189."""
 
     def __init__(self, diffuse=[0.6, 0.5, 0.7], specular=[0.8, 0.8, 0.8], min_spec=1, device="cuda"):
         super().__init__()
@@ -217,6 +278,19 @@ class Phong(_Unsupported):
         self.diffuse = torch.rand_like(self.diffuse, requires_grad=True)
         return self
 
+    def exponent(self):
+        """min_spec + exp(shine) (bsdfs.py:181), in float32 as the reference's tensor op."""
+        return float(self.min_spec + self.shine.detach().float().exp())
+
+    def _component(self):
+        d = self.diffuse.detach().float().cpu().tolist()
+        sp = self.specular.detach().float().cpu().tolist()
+        return (_lib.NRT_BSDF_PHONG, None, _lib.ACT["none"], _pad(d + sp + [self.exponent()]))
+
+    def eval_and_pdf(self, it, wo, active=True):
+        """bsdfs.py:176-189 (not masked)."""
+        return self._eval_hip(it, wo, active)
+
 
 def fresnel_diff_refl(eta):
     """bsdfs.py:220-235 (Mitsuba's diffuse Fresnel reflectance fit)."""
@@ -227,8 +301,8 @@ def fresnel_diff_refl(eta):
         4.98554 * inv ** 4 - 1.36881 * inv ** 5
 
 
-class Plastic(_Unsupported):
-    """bsdfs.py:238-270 (constructor, parameters, random)."""
+class Plastic(BSDF):
+    """bsdfs.py:238-325."""
 
     def __init__(self, diffuse=[0.5, 0.5, 0.5], specular=[1., 1., 1.], int_ior: float = 1.49,
                  ext_ior: float = 1.000277, device="cuda"):
@@ -256,10 +330,28 @@ class Plastic(_Unsupported):
         self.diffuse = torch.rand_like(self.diffuse, requires_grad=True)
         return self
 
+    def _component(self):
+        """diffuse rgb, specular rgb, eta, 1/eta, 1 - fdr_int, inv_eta_2, spec_sample_weight: the
+        constants as the reference holds them, Python doubles (bsdfs.py:197, 254-259, 278)."""
+        d = self.diffuse.detach().float().cpu().tolist()
+        sp = self.specular.detach().float().cpu().tolist()
+        ssw = float(self.spec_sample_weight().detach().float())
+        return (_lib.NRT_BSDF_PLASTIC, None, _lib.ACT["none"],
+                _pad(d + sp + [self.eta, 1 / self.eta, 1 - self.fdr_int, self.inv_eta_2, ssw]))
 
-class Bidirectional(_Unsupported):
-    """bsdfs.py:409-440: front BSDF for cos(theta_i) > 0, back (default: the front one) with z
-    inverted below the surface."""
+    def eval_and_pdf(self, it, wo, active=True):
+        """bsdfs.py:271-291 (not masked)."""
+        return self._eval_hip(it, wo, active)
+
+
+class Bidirectional(BSDF):
+    """bsdfs.py:409-453: front BSDF for cos(theta_i) > 0, back (default: the front one) with z
+    inverted below the surface.  On the HIP path: any leaf on both sides, two different analytic
+    leaves, or a ComposeSpatialVarying on both sides (every component two-sided: the weights
+    depend on p only, so the spectrum is the same).  A distinct NeuralBSDF behind is refused."""
+
+    _mask_spectrum = True
+    _mask_pdf = True
 
     def __init__(self, front, back=None):
         super().__init__()
@@ -269,3 +361,55 @@ class Bidirectional(_Unsupported):
     def parameters(self):
         from itertools import chain
         return chain(self.front.parameters(), self.back.parameters())
+
+    def _leaf(self, b):
+        if isinstance(b, (Bidirectional, ComposeSpatialVarying)) or not hasattr(b, "_component"):
+            raise _lib.NrtError(f"Bidirectional({type(b).__name__}) has no HIP implementation "
+                                "(supported: a leaf BSDF, or one ComposeSpatialVarying on both "
+                                "sides)")
+        return b._component()
+
+    def _component(self):
+        if self.back is not self.front and (isinstance(self.front, NeuralBSDF) or
+                                            isinstance(self.back, NeuralBSDF)):
+            raise _lib.NrtError("Bidirectional with a NeuralBSDF needs the same NeuralBSDF on both "
+                                "sides on the HIP path (one MLP evaluation per ray); a distinct "
+                                "NeuralBSDF behind is not supported")
+        kind, mh, act, params = self._leaf(self.front)
+        if self.back is self.front:
+            return (kind, mh, act, params, (kind, act, params))
+        bk, _, bact, bparams = self._leaf(self.back)
+        return (kind, mh, act, params, (bk, bact, bparams))
+
+    def _lowered(self):
+        """Bidirectional(ComposeSpatialVarying([...])) as the mixture of two-sided components."""
+        mix = self.front
+        cached = getattr(self, "_nrt_lowered", None)
+        if cached is None or cached[0] is not mix or cached[1] != [id(b) for b in mix.bsdfs]:
+            w = ComposeSpatialVarying.__new__(ComposeSpatialVarying)
+            nn.Module.__init__(w)
+            w.bsdfs = [Bidirectional(b) for b in mix.bsdfs]
+            w.sp_var_fn = mix.sp_var_fn
+            w.preprocess = mix.preprocess
+            cached = (mix, [id(b) for b in mix.bsdfs], w)
+            object.__setattr__(self, "_nrt_lowered", cached)
+        return cached[2]
+
+    def nrt(self):
+        if isinstance(self.front, ComposeSpatialVarying):
+            if self.back is not self.front:
+                raise _lib.NrtError("Bidirectional of a ComposeSpatialVarying needs the same "
+                                    "mixture on both sides on the HIP path")
+            return self._lowered().nrt()
+        wrapper = getattr(self, "_nrt_single", None)
+        if wrapper is None:
+            wrapper = ComposeSpatialVarying.__new__(ComposeSpatialVarying)
+            nn.Module.__init__(wrapper)
+            wrapper.bsdfs = [self]
+            wrapper.sp_var_fn = None
+            object.__setattr__(self, "_nrt_single", wrapper)
+        return wrapper.nrt()
+
+    def eval_and_pdf(self, it, wo, active=True):
+        """bsdfs.py:434-453 (spectrum and pdf are zero where ~active or wi.z == 0)."""
+        return self._eval_hip(it, wo, active)

@@ -109,6 +109,42 @@ def fresnel_conductor(cos_t, eta_r: float, eta_i: float):
 
 # ---- SDF values and gradients with autograd ---------------------------------------------------
 
+def reflect(n, v):
+    """bsdfs.py:121-123."""
+    return 2 * (n * v).sum(keepdim=True, dim=-1) * n - v
+
+
+def invert_z(xyz):
+    """bsdfs.py:404-406."""
+    x, y, z = xyz.split(1, dim=-1)
+    return torch.cat([x, y, -z], dim=-1)
+
+
+def fresnel(cos_t, eta: float):
+    """bsdfs.py:193-218, its first result."""
+    out_mask = cos_t >= 0
+    inv_eta = 1 / eta
+    eta_it = torch.where(out_mask, eta, inv_eta)
+    eta_ti = torch.where(out_mask, inv_eta, eta)
+    cos_tt_sqr = -(-cos_t * cos_t + 1) * (eta_ti * eta_ti) + 1
+    cos_t_abs = cos_t.abs()
+    cos_tt_abs = cos_tt_sqr.clamp(min=1e-10).sqrt()
+    a_s = (-eta_it * cos_tt_abs + cos_t_abs) / (eta_it * cos_tt_abs + cos_t_abs)
+    a_p = (-eta_it * cos_t_abs + cos_tt_abs) / (eta_it * cos_t_abs + cos_tt_abs)
+    r = 0.5 * (a_s.square() + a_p.square())
+    if eta == 1:
+        return torch.zeros_like(r)
+    return torch.where(cos_t_abs == 0, torch.ones_like(r), r)
+
+
+def _world_normal(it):
+    """it.frame[..., 2]: the last column of [s t n] (interaction.py:9-27)."""
+    frame = getattr(it, "frame", None)
+    if frame is not None:
+        return frame[..., 2]
+    return F.normalize(it.n, eps=1e-7, dim=-1)
+
+
 def needs_grad(*modules):
     """True when autograd is on and any parameter of the given objects requires a gradient."""
     if not torch.is_grad_enabled():
@@ -434,10 +470,45 @@ def shadowed_light(shapes, lights, it, active, w_isect):
 
 
 def bsdf_eval(bsdf, it, wo, active, feat=None):
-    """eval_and_pdf of the supported BSDFs (bsdfs.py:108-118, 364-388, 515-536, 634-637).
+    """eval_and_pdf of the supported BSDFs (bsdfs.py:108-118, 176-189, 271-291, 364-388, 434-453,
+    515-536, 634-637).
     `feat`: param_rusin2(it.wi, wo) when the caller already has it."""
-    from .bsdf.bsdfs import ComposeSpatialVarying, Conductor, Diffuse, NeuralBSDF, identity_div_pi
+    from .bsdf.bsdfs import (Bidirectional, ComposeSpatialVarying, Conductor, Diffuse, NeuralBSDF,
+                             Phong, Plastic, identity_div_pi)
     from .neural_blocks import mlp_multi, same_shape
+    if isinstance(bsdf, Bidirectional):
+        # bsdfs.py:434-453: the back side at (invert_z(wi), invert_z(wo)), the frame unchanged
+        import copy
+        cos_i = it.wi[..., 2]
+        front, back = (cos_i > 0) & active, (cos_i < 0) & active
+        f_f, p_f = bsdf_eval(bsdf.front, it, wo, front)
+        flipped = copy.copy(it)
+        flipped.wi = invert_z(it.wi)
+        f_b, p_b = bsdf_eval(bsdf.back, flipped, invert_z(wo), back)
+        f = torch.where(front.unsqueeze(-1), f_f,
+                        torch.where(back.unsqueeze(-1), f_b, torch.zeros_like(f_b)))
+        pdf = torch.where(front, p_f, torch.where(back, p_b, torch.zeros_like(p_b)))
+        return f, pdf
+    if isinstance(bsdf, Phong):
+        # bsdfs.py:176-189: the world normal against the local wi, as written there
+        R = reflect(_world_normal(it), it.wi)
+        expo = bsdf.min_spec + bsdf.shine.to(wo.device).exp()
+        spectral = (R * wo).sum(dim=-1).clamp(min=1e-20).pow(expo)
+        f = it.wi[..., 2].unsqueeze(-1) * bsdf.diffuse.to(wo.device) / math.pi + \
+            spectral.unsqueeze(-1) * bsdf.specular.to(wo.device) / math.pi
+        return f, wo[..., 2] / math.pi
+    if isinstance(bsdf, Plastic):
+        # bsdfs.py:271-291; eta is a Python float there and carries no gradient
+        f_i = fresnel(it.wi[..., 2], bsdf.eta)
+        f_o = fresnel(wo[..., 2], bsdf.eta)
+        pdf = wo[..., 2] / math.pi
+        f = (bsdf.diffuse.to(wo.device).expand_as(it.p) / (1 - bsdf.fdr_int)) * bsdf.inv_eta_2 * \
+            (pdf * (1 - f_i) * (1 - f_o)).unsqueeze(-1)
+        ssw = bsdf.spec_sample_weight().to(wo.device)
+        prob_specular = ssw * f_i
+        prob_diffuse = (1 - f_i) * (1 - ssw)
+        prob_diffuse = prob_diffuse / (prob_specular + prob_diffuse)
+        return f, pdf * prob_diffuse
     if isinstance(bsdf, ComposeSpatialVarying):
         k = bsdf.sp_var_fn(bsdf.preprocess(it.p)).reshape(it.p.shape[:-1] + (len(bsdf.bsdfs),))
         setattr(it, "nonnormalized_weights", k)
@@ -460,7 +531,7 @@ def bsdf_eval(bsdf, it, wo, active, feat=None):
                 f = b.act(pre[id(b)])
                 pdf = torch.ones(f.shape[:-1], device=f.device)
             else:
-                f, pdf = bsdf_eval(b, it, wo, active, feat)
+                f, pdf = bsdf_eval(b, it, wo, active, feat if isinstance(b, NeuralBSDF) else None)
             parts.append(torch.cat([f, pdf.reshape(f.shape[:-1] + (1,))], dim=-1))
         spec_pdf = torch.stack(parts, dim=-1)
         setattr(it, "normalized_weights", k)
@@ -512,6 +583,45 @@ def direct_sample(it, active, bsdf, lights, lead, device, shapes=None, w_isect=F
     return torch.where(ae.unsqueeze(-1), result + f * le, result)
 
 
+def bounce_uniforms(bsdf, sampler, lead, P, dev, injected=None):
+    """One bounce's BSDF-sampling randomness -> (u_comp [P, nc, 2], u_sel [P], u_lobe [P, nc] or
+    None).  Drawn in the reference's order: per component, in component order, a Plastic's lobe
+    draw sampler.sample(p_spec.shape) (bsdfs.py:304) and then the component's (.., 2) draw
+    (:98, :163, :309, :628); the selection draw last.  `injected`: (u_comp, u_sel[, u_lobe])."""
+    from .bsdf.bsdfs import Plastic
+    parts = getattr(bsdf, "bsdfs", [bsdf])
+    nc = len(parts)
+    plastic = [isinstance(b, Plastic) for b in parts]
+    if injected is not None:
+        u = [t.to(dev).float().reshape(P, -1).contiguous() for t in injected]
+        if any(plastic) and len(u) < 3:
+            raise _lib.NrtError("uniforms need (u_comp, u_sel, u_lobe) for a Plastic component")
+        return u[0], u[1], (u[2] if any(plastic) else None)
+    draws, lobes = [], []
+    for is_plastic in plastic:
+        if is_plastic:
+            lobes.append(sampler.sample(tuple(lead)).to(dev).reshape(P, 1))
+        elif any(plastic):
+            lobes.append(torch.zeros(P, 1, device=dev))
+        draws.append(sampler.sample(tuple(lead) + (2,), device=dev).reshape(P, 1, 2))
+    u_comp = torch.cat(draws, dim=1).contiguous()
+    u_sel = sampler.sample((P,), device=dev).contiguous()
+    return u_comp, u_sel, (torch.cat(lobes, dim=1).contiguous() if any(plastic) else None)
+
+
+def path_bounce(bh, lh, sh, shadow, occ, max_steps, eps, p, n, wi, P, act, thr, res, u_comp, u_sel,
+                u_lobe, rays_out, ws):
+    """nrt_path_bounce, or nrt_path_bounce_ex when the mixture has a Plastic lobe draw."""
+    if u_lobe is None:
+        _lib.call("nrt_path_bounce", bh, lh, sh, shadow, occ, max_steps, eps, p, n, wi, P, act, thr,
+                  res, _lib.ptr(u_comp), _lib.ptr(u_sel), rays_out, ws, _lib.precision_code(),
+                  _lib.stream())
+    else:
+        _lib.call("nrt_path_bounce_ex", bh, lh, sh, shadow, occ, max_steps, eps, p, n, wi, P, act,
+                  thr, res, _lib.ptr(u_comp), _lib.ptr(u_sel), _lib.ptr(u_lobe), rays_out, ws,
+                  _lib.precision_code(), _lib.stream())
+
+
 def path_sample(shapes, rays, bsdf, lights, max_depth, training, sampler, uniforms=None,
                 w_isect=False):
     """Path.sample with autograd (integrators.py:275-354).  Per bounce the emitter term is
@@ -534,7 +644,6 @@ def path_sample(shapes, rays, bsdf, lights, max_depth, training, sampler, unifor
     original_active = active.clone()
     shadow, occ = _emitter_mode(w_isect)
     P = active.numel()
-    nc = len(getattr(bsdf, "bsdfs", [bsdf]))
     act = active.reshape(-1).to(torch.uint8).contiguous()
     thr = torch.ones(P, 3, device=dev)      # detached throughput, updated by the bounce
     scratch = torch.zeros(P, 3, device=dev)  # the bounce's own (gradient-free) emitter sum
@@ -549,22 +658,16 @@ def path_sample(shapes, rays, bsdf, lights, max_depth, training, sampler, unifor
         # a snapshot: autograd keeps this factor for the backward, and the bounce below updates
         # `thr` in place through a raw pointer (no version bump for autograd to catch)
         result = result + thr.clone().reshape(*lead, 3) * term
-        if uniforms is not None:
-            u_comp, u_sel = (u.to(dev).float().reshape(P, -1).contiguous() for u in uniforms[depth])
-        else:
-            draws = [sampler.sample(tuple(lead) + (2,), device=dev).reshape(P, 1, 2)
-                     for _ in range(nc)]
-            u_comp = torch.cat(draws, dim=1).contiguous()
-            u_sel = sampler.sample((P,), device=dev).contiguous()
+        u_comp, u_sel, u_lobe = bounce_uniforms(bsdf, sampler, lead, P, dev,
+                                                uniforms[depth] if uniforms is not None else None)
         with torch.no_grad():
             cp = curr.p.detach().reshape(P, 3).contiguous()
             cn = curr.n.detach().reshape(P, 3).contiguous()
             cw = curr.wi.detach().reshape(P, 3).contiguous()
-            _lib.call("nrt_path_bounce", _bsdf_handle(bsdf), _light_handle(lights), sh, shadow,
-                      occ, int(shapes.max_steps), float(shapes.epsilon), _lib.ptr(cp), _lib.ptr(cn),
-                      _lib.ptr(cw), P, _lib.ptr(act), _lib.ptr(thr), _lib.ptr(scratch),
-                      _lib.ptr(u_comp), _lib.ptr(u_sel), _lib.ptr(rays_out), _lib.ptr(ws),
-                      _lib.precision_code(), _lib.stream())
+            path_bounce(_bsdf_handle(bsdf), _light_handle(lights), sh, shadow, occ,
+                        int(shapes.max_steps), float(shapes.epsilon), _lib.ptr(cp), _lib.ptr(cn),
+                        _lib.ptr(cw), P, _lib.ptr(act), _lib.ptr(thr), _lib.ptr(scratch),
+                        u_comp, u_sel, u_lobe, _lib.ptr(rays_out), _lib.ptr(ws))
         if depth + 1 == max_depth or not bool(act.any()):
             break  # the reference's last spawn is never shaded (:309, :342)
         # the sampled local direction carries no gradient in the reference either: NeuralBSDF /

@@ -230,7 +230,8 @@ class Direct(Integrator):
         # it.normalized_weights / nonnormalized_weights (bsdfs.py:516-536: sigmoid(sp_var_fn(p))
         # on EVERY ray, misses included) are evaluated on first access (HipInteraction), so a
         # render that never reads them pays nothing for them
-        it._nrt_spatial = bsdf
+        # (a two-sided mixture has its front mixture's weights: they depend on p only)
+        it._nrt_spatial = bsdf.front if hasattr(getattr(bsdf, "front", None), "sp_var_fn") else bsdf
         per_cam = getattr(lights, "per_camera", lambda: None)()
         if per_cam is not None:
             # one point light per camera (lights.py:91 broadcasts location[n] over camera n's
@@ -288,8 +289,10 @@ class Path(Integrator):
 
     Randomness: each BSDF component draws ``sampler.sample(shape + (2,))`` in component order, as
     in the reference; the component selection (torch.multinomial there) is the inverse CDF of the
-    spatial weights at one more uniform draw.  ``uniforms=[(u_comp, u_sel), ...]`` (one pair per
-    bounce) replaces the draws, for parity tests.
+    spatial weights at one more uniform draw.  A Plastic component first draws its lobe uniform
+    ``sampler.sample(shape)`` (bsdfs.py:304).  ``uniforms=[(u_comp, u_sel[, u_lobe]), ...]`` (one
+    tuple per bounce; ``u_lobe [.., n_components]`` when the mixture has a Plastic) replaces the
+    draws, for parity tests.
     """
 
     # secondary intersections march only the rays whose path is still active (compacted on the
@@ -305,6 +308,7 @@ class Path(Integrator):
 
     def sample(self, shapes, rays, bsdf, **kwargs):
         from ..shapes.sdfs import sdf_handle
+        from ..differentiable import bounce_uniforms, path_bounce
         sampler = kwargs.get("sampler", self.sampler)
         lights = kwargs.get("lights", self.lights)
         shadow, occ = _emitter_mode(kwargs.get("w_isect", False))
@@ -323,7 +327,6 @@ class Path(Integrator):
             return result, active, it
         original_active = active.clone()
         P = active.numel()
-        nc = len(getattr(bsdf, "bsdfs", [bsdf]))
         act = active.reshape(-1).to(torch.uint8).contiguous()
         thr = torch.ones(P, 3, device=dev)
         res = result.reshape(P, 3)
@@ -333,20 +336,15 @@ class Path(Integrator):
         sh = sdf_handle(shapes.sdf)
         curr = it
         for depth in range(self.max_depth):
-            if uniforms is not None:
-                u_comp, u_sel = (u.to(dev).float().reshape(P, -1).contiguous() for u in uniforms[depth])
-            else:
-                draws = [sampler.sample(tuple(lead) + (2,), device=dev).reshape(P, 1, 2)
-                         for _ in range(nc)]
-                u_comp = torch.cat(draws, dim=1).contiguous()
-                u_sel = sampler.sample((P,), device=dev).contiguous()
-            _lib.call("nrt_path_bounce", _bsdf_handle(bsdf), _light_handle(lights), sh,
-                      shadow, occ, int(shapes.max_steps), float(shapes.epsilon),
-                      _lib.ptr(curr.p.reshape(P, 3).contiguous()),
-                      _lib.ptr(curr.n.reshape(P, 3).contiguous()),
-                      _lib.ptr(curr.wi.reshape(P, 3).contiguous()), P, _lib.ptr(act),
-                      _lib.ptr(thr), _lib.ptr(res), _lib.ptr(u_comp), _lib.ptr(u_sel),
-                      _lib.ptr(rays_out), _lib.ptr(ws), _lib.precision_code(), _lib.stream())
+            u_comp, u_sel, u_lobe = bounce_uniforms(
+                bsdf, sampler, lead, P, dev, uniforms[depth] if uniforms is not None else None)
+            path_bounce(_bsdf_handle(bsdf), _light_handle(lights), sh, shadow, occ,
+                        int(shapes.max_steps), float(shapes.epsilon),
+                        _lib.ptr(curr.p.reshape(P, 3).contiguous()),
+                        _lib.ptr(curr.n.reshape(P, 3).contiguous()),
+                        _lib.ptr(curr.wi.reshape(P, 3).contiguous()), P, _lib.ptr(act),
+                        _lib.ptr(thr), _lib.ptr(res), u_comp, u_sel, u_lobe, _lib.ptr(rays_out),
+                        _lib.ptr(ws))
             if depth + 1 == self.max_depth:
                 break  # the reference's last spawn is never shaded (:309, :342)
             # the spawned rays of the still-active paths only (one host synchronisation, as the
