@@ -810,14 +810,10 @@ int nrt_nerfle_forward(const nrt_mlp* first, const nrt_mlp* second, const float*
     auto kern = k_nerfle16<kNerfWaves, kNerfTiles>;
     const size_t lds = ring::KEngine<kNerfWaves, kNerfMaxF, kNerfDma>::lds_bytes(pd);
     if (int rc = set_lds(kern, lds)) return rc;
-    int dev = 0, cus = 0, per_cu = 0;
-    NRT_HIP(hipGetDevice(&dev));
-    NRT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    NRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kNerfWaves, lds));
     // persistent grid: every resident block slot (independent blocks on a CU run out of phase,
     // so one block's layer-boundary bubbles are filled by the other's MFMAs)
-    const int64_t want = ceil_div64((int64_t)n, 32 * kNerfTiles * kNerfWaves);
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)std::max(per_cu, 1) * cus));
+    const int blocks = resident_grid(kern, 64 * kNerfWaves, lds,
+                                     ceil_div64((int64_t)n, 32 * kNerfTiles * kNerfWaves));
     ProfScope prof("k_nerfle", st);
     kern<<<dim3(blocks), dim3(64 * kNerfWaves), lds, st>>>(pd, rays, P, ts, S, light, alpha, rgb_raw);
     if (int rc = check_launch("k_nerfle16")) return rc;

@@ -112,7 +112,7 @@ int nrt_sdf_eval(const nrt_sdf* s, const float* p, int64_t M, float* out, int pr
   if (prim_lanes(s)) return prim_eval(s, p, M, out, (hipStream_t)stream);
   if ((precision == NRT_FP32_SPLIT || precision == NRT_MIXED) && ring3_supported(s) &&
       option(OPT_RING32) != 0)
-    return ring_eval3(s, p, M, out, (hipStream_t)stream);
+    return ring3_launch(s, Pass::Eval, p, M, MarchArgs{}, {.thr = out}, (hipStream_t)stream);
   const bool f16 = precision == NRT_FP16;
   int hidden, ke;
   sdf_dims(s, hidden, ke);
@@ -337,13 +337,13 @@ int launch_occlusion(const nrt_sdf* s, const float* rays, int64_t P, const int32
     ma.evals = profile_eval_counter();
     if (f16 && ring_supported(s) && option(OPT_RING16) != 0) {
       ProfScope prof("k_occlusion", st);
-      return ring_march16_launch(s, rays, P, ma, nullptr, nullptr, nullptr, st, false, visible);
+      return ring16_launch(s, Pass::Occlusion, rays, P, ma, {.visible = visible}, st);
     }
     if (!f16 && ring32_supported(s) && option(OPT_RING32) != 0) {
       ProfScope prof("k_occlusion", st);
       const bool split = (precision == NRT_FP32_SPLIT || precision == NRT_MIXED) && ring3_supported(s);
-      return split ? ring3_launch(s, rays, P, ma, nullptr, nullptr, nullptr, st, 4, visible)
-                   : ring_occlusion32(s, rays, P, ma, visible, st);
+      return split ? ring3_launch(s, Pass::Occlusion, rays, P, ma, {.visible = visible}, st)
+                   : ring32_launch(s, Pass::Occlusion, rays, P, ma, {.visible = visible}, st);
     }
   }
   if (prim_lanes(s)) {

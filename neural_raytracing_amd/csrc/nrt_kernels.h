@@ -1064,14 +1064,11 @@ template <int KH, int KQ, int WV, int ACT, bool MX = false>
 __global__ void __launch_bounds__(64 * WV, 1) k_scan_best3(NRT_MARCH_ARGS) {
   march_body<RingPol3<KH, KQ, WV, ACT>, 1, MX>(s, m, rays, P, a, NRT_MARCH_PASS);
 }
-// sdf(p) of P points on the ring engines (nrt_sdf_eval: fp32-split and FP32 precision)
+// sdf(p) of P points on the split engine (nrt_sdf_eval at fp32-split / mixed; the other
+// precisions evaluate on the per-wave k_sdf_eval)
 template <int KH, int KQ, int WV, int ACT>
 __global__ void __launch_bounds__(64 * WV, 1) k_sdf_eval3(NRT_MARCH_ARGS) {
   march_body<RingPol3<KH, KQ, WV, ACT>, 2>(s, m, rays, P, a, NRT_MARCH_PASS);
-}
-template <int KH, int KE, int WV, int ACT>
-__global__ void __launch_bounds__(64 * WV, 1) k_sdf_eval32r(NRT_MARCH_ARGS) {
-  march_body<RingPol32<KH, KE, WV, ACT>, 2>(s, m, rays, P, a, NRT_MARCH_PASS);
 }
 #undef NRT_MARCH_PASS
 #undef NRT_MARCH_ARGS

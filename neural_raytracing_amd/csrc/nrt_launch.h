@@ -121,6 +121,29 @@ static inline int check_launch(const char* what) {
   return NRT_OK;
 }
 
+// blocks of `threads` threads and `lds` dynamic LDS bytes that stay resident on one CU; 1 when
+// the query fails (a real failure still surfaces at the launch's check_launch)
+template <class K>
+int blocks_per_cu(K kern, int threads, size_t lds) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern),
+                                                   threads, lds) != hipSuccess)
+    return 1;
+  return std::max(per_cu, 1);
+}
+
+// the grid of a persistent kernel: `want` blocks, but no more than stay resident at once
+template <class K>
+int resident_grid(K kern, int threads, size_t lds, int64_t want) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  }
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * blocks_per_cu(kern, threads, lds)));
+}
+
 static inline int sdf_dims(const nrt_sdf* s, int& hidden, int& ke) {
   hidden = 32; ke = 16;
   if (s->mlp) { hidden = s->mlp->desc.hidden; ke = s->mlp->host_dev.ke; }
@@ -168,23 +191,90 @@ int ring_dispatch(const nrt_sdf* s, F&& f) {
   return NRT_EINVAL;
 }
 
+// ---- one launch of a ring engine's march_body kernel (nrt_kernels.h) ----
+// The passes of the three engines; each engine's launcher (ring16_launch / ring32_launch /
+// ring3_launch) maps a pass to its kernel instantiation and profile name in one switch.
+enum class Pass {
+  March,        // the plain march (packed t; with MarchArgs::primary the coarse scan's keys too)
+  ScanBest,     // thr = -1000 sdf(best) at the argmins in keys
+  Occlusion,    // the shadow march (MarchArgs::occ_max_t / count): visible
+  RefineMarch,  // NRT_MIXED's march instantiation: on the FP16 engine the march that flags its
+                // undecidable steps (MarchArgs::amb), on the split engine the re-march of those rays
+  RefineScan,   // NRT_MIXED's sdf(best) over both candidates (split engine)
+  Eval,         // sdf(p) of [P, 3] points -> thr (split engine)
+};
+// what a pass writes; the pointers it does not write stay null
+struct MarchOut {
+  float* t = nullptr;                  // March / RefineMarch: (hit, t) packed for k_march_finish
+  uint8_t* visible = nullptr;          // Occlusion
+  float* thr = nullptr;                // ScanBest / RefineScan / Eval
+  unsigned long long* keys = nullptr;  // the scan keys; the entry that owns them clears them (below)
+};
+// Scan keys: the intersect entry (ring_march, ring_march32, ring_march3, ring_march_mixed) sets
+// them to all-ones once, before its first launch, when the rays are primary; no launcher does.
+
+struct MarchLaunch {
+  bool stage_lines = false;    // the plain march: per-wave line stages behind the block's LDS
+  // drop the stages where they would cost a resident block per CU.  True for the FP16 engine
+  // only: the FP32 and split marches keep their stages unconditionally.  ADVICE.md item 2 (open)
+  // asks for the guard on all three; that changes which launches stage, so not without measuring.
+  bool keep_blocks_per_cu = false;
+  bool schedule_options = true;  // option "march_blocks" and the queue-counter reset (not Eval)
+};
+
+// `kern` over P work items (16 a wave) on a persistent grid: LDS size (+ stages), set_lds,
+// resident grid, the schedule options, profile scope `name`, launch, check_launch
+template <class K>
+int launch_march(K kern, const char* name, int threads, size_t lds, const nrt_sdf* s,
+                 const float* rays, int64_t P, MarchArgs a, const MarchOut& o, MarchLaunch how,
+                 hipStream_t st) {
+  const int waves = threads / 64;
+  if (how.stage_lines) {
+    const size_t lds0 = lds;
+    stage_lds(a, lds, waves);
+    if (how.keep_blocks_per_cu && a.stage && kLdsBytes / lds != kLdsBytes / lds0) { a.stage = 0; lds = lds0; }
+    if (a.stage) profile_count_staged();
+  }
+  if (int rc = set_lds(kern, lds)) return rc;
+  // persistent grid: every resident block slot, but no more waves than 16-ray tiles -- a small
+  // batch (a training step's 38,400 rays) spreads over every CU, the job lists giving idle lanes
+  // scan segments (measured: the mixed training step 33.5 -> 31.6 ms against 32 rays a wave)
+  int blocks = resident_grid(kern, threads, lds, ceil_div64(P, 16 * waves));
+  if (how.schedule_options) {
+    // option "march_blocks": force the grid (tests check that results do not depend on the schedule)
+    if (const int64_t f = option(OPT_MARCH_BLOCKS)) blocks = (int)std::min<int64_t>(f, 1 << 20);
+    if (a.queue) NRT_HIP(hipMemsetAsync(a.queue, 0, sizeof(unsigned int), st));
+  }
+  ProfScope prof(name, st);
+  // p / n / raw_n: written by k_march_finish (the march packs hit into t's sign bit)
+  kern<<<dim3(blocks), dim3(threads), lds, st>>>(s->host_dev, s->mlp->host_dev, rays, P, a, o.t,
+                                                 o.visible, nullptr, nullptr, nullptr, o.thr, o.keys);
+  return check_launch(name);
+}
+
+// after a ring march: unpack (hit, t), p / n / raw_n and the hit list, coalesced (a template,
+// so that only the translation units that call it carry the kernel)
+template <int = 0>
+int march_finish(const float* rays, int64_t P, float* t, uint8_t* hit, float* p, float* n,
+                        float* raw_n, int32_t* idx, int32_t* cnt, hipStream_t st) {
+  k_march_finish<><<<dim3(std::min<int64_t>(ceil_div64(P, 256), 2048)), dim3(256), 0, st>>>(
+      rays, P, t, hit, p, n, raw_n, idx, cnt);
+  return check_launch("k_march_finish");
+}
+
 int ring_march(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma, float* t,
                uint8_t* hit, float* p, float* n, float* raw_n, float* thr, int32_t* idx,
                int32_t* cnt, unsigned long long* keys, hipStream_t st);
-// k_march16 alone (packed t, scan keys; the caller initialises keys): NRT_MIXED's first pass;
-// with `visible`, the shadow march k_occl16 instead (MarchArgs::occ_max_t / count)
-int ring_march16_launch(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma,
-                        float* t, float* thr, unsigned long long* keys, hipStream_t st,
-                        bool best16, uint8_t* visible = nullptr);
+// one FP16 pass: March (k_march16), ScanBest (k_scan_best16), Occlusion (k_occl16), RefineMarch
+// (k_march16, the flagging instantiation)
+int ring16_launch(const nrt_sdf* s, Pass pass, const float* rays, int64_t P, const MarchArgs& ma,
+                  const MarchOut& out, hipStream_t st);
 
 // ---- FP32 ring engine (nrt_ring_march32.hip) ----
 // SDF MLPs with a compiled FP32 ring kernel: hidden 128 / 256, F = 16 / 32 with 3 inputs and no
 // latent (ke = 48 / 80), <= 16 outputs, softplus or leaky_relu; any layer count and skip period.
 // Refreshed handles qualify (nrt_mlp_refresh re-gathers stream32).
 constexpr int kRing32Waves = 8;
-inline size_t ring32_bias_bytes(const nrt_sdf* s) {
-  return (size_t)(s->mlp->desc.num_layers + 2) * s->mlp->host_dev.bias16_stride * 4;
-}
 inline size_t ring32_sphere_bytes(const nrt_sdf* s) {
   // the per-sphere table (ring3) or the FP32 ring's pair table (ring32::build_sphere_pairs32)
   if (s->host_dev.kind != 2) return 0;
@@ -199,14 +289,32 @@ inline bool ring32_supported(const nrt_sdf* s) {
   if (!((m.hidden == 128 || m.hidden == 256) && (m.ke == 48 || m.ke == 80) && m.in_size == 3 &&
         m.latent == 0 && m.out <= 16 && (act == NRT_ACT_SOFTPLUS || act == NRT_ACT_LEAKY_RELU)))
     return false;
-  return ring32_sphere_bytes(s) + ring32_bias_bytes(s) <= 48 * 1024;
+  return ring32_sphere_bytes(s) + ring_bias_bytes(s) <= 48 * 1024;
+}
+// call F.template operator()<KH, KE, ACT>() for the SDF's FP32 ring configuration
+template <class F>
+int ring32_dispatch(const nrt_sdf* s, F&& f) {
+  const MlpDev& m = s->mlp->host_dev;
+  const bool sp = s->mlp->desc.activation == NRT_ACT_SOFTPLUS;
+#define NRT_RING_CASE(H, KEV)                                            \
+  if (m.hidden == H && m.ke == 4 * KEV)                                  \
+    return sp ? f.template operator()<H / 4, KEV, ACT_SOFTPLUS>()        \
+              : f.template operator()<H / 4, KEV, ACT_LEAKY>();
+  NRT_RING_CASE(256, 12)
+  NRT_RING_CASE(256, 20)
+  NRT_RING_CASE(128, 12)
+  NRT_RING_CASE(128, 20)
+#undef NRT_RING_CASE
+  set_error("FP32 ring engine: unsupported SDF configuration");
+  return NRT_EINVAL;
 }
 int ring_march32(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma, float* t,
                  uint8_t* hit, float* p, float* n, float* raw_n, float* thr, int32_t* idx,
                  int32_t* cnt, unsigned long long* keys, hipStream_t st);
-// k_scan_best32 alone: thr = -1000 sdf(best) on the FP32 engine at the argmins in keys
-int ring_scan_best32(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma,
-                     float* thr, unsigned long long* keys, hipStream_t st);
+// one FP32 pass: March (k_march32), ScanBest (k_scan_best32; also an FP16 march's sdf(best),
+// option "scan_best32"), Occlusion (k_occl32)
+int ring32_launch(const nrt_sdf* s, Pass pass, const float* rays, int64_t P, const MarchArgs& ma,
+                  const MarchOut& out, hipStream_t st);
 // ---- fp32-split ring engine (nrt_ring_march3.hip, nrt_ring3.h): the ring32 configurations,
 // from a handle packed by nrt_mlp_create or refreshed by nrt_mlp_refresh (which re-splits it)
 constexpr int kRing3Waves = 8;
@@ -215,19 +323,30 @@ inline bool ring3_supported(const nrt_sdf* s) {
   const MlpDev& m = s->mlp->host_dev;
   return ring32_supported(s) && (m.ke3 == 64 || m.ke3 == 96);
 }
-int ring_eval3(const nrt_sdf* s, const float* pts, int64_t M, float* out, hipStream_t st);
+// call F.template operator()<KH, KQ, ACT>() for the SDF's split ring configuration
+template <class F>
+int ring3_dispatch(const nrt_sdf* s, F&& f) {
+  const MlpDev& m = s->mlp->host_dev;
+  const bool sp = s->mlp->desc.activation == NRT_ACT_SOFTPLUS;
+#define NRT_RING_CASE(H, KQV)                                            \
+  if (m.hidden == H && m.ke3 == 32 * KQV)                                \
+    return sp ? f.template operator()<H / 32, KQV, ACT_SOFTPLUS>()       \
+              : f.template operator()<H / 32, KQV, ACT_LEAKY>();
+  NRT_RING_CASE(256, 2)
+  NRT_RING_CASE(256, 3)
+  NRT_RING_CASE(128, 2)
+  NRT_RING_CASE(128, 3)
+#undef NRT_RING_CASE
+  set_error("fp32-split ring engine: unsupported SDF configuration");
+  return NRT_EINVAL;
+}
 int ring_march3(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma, float* t,
                 uint8_t* hit, float* p, float* n, float* raw_n, float* thr, int32_t* idx,
                 int32_t* cnt, unsigned long long* keys, hipStream_t st);
-// the split engine's launches alone: which = 0 k_march3 (+ k_scan_best3 when primary), 1
-// k_scan_best3 (the caller initialises keys); 2 / 3 the same as NRT_MIXED's refinement passes;
-// 4 the shadow march k_occl3 (visible -> hit)
-int ring3_launch(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma, float* t,
-                 float* thr, unsigned long long* keys, hipStream_t st, int which,
-                 uint8_t* hit = nullptr);
-// the FP32 ring's shadow march k_occl32
-int ring_occlusion32(const nrt_sdf* s, const float* rays, int64_t P, const MarchArgs& ma,
-                     uint8_t* visible, hipStream_t st);
+// one split-engine pass: March (k_march3), ScanBest (k_scan_best3), Occlusion (k_occl3),
+// RefineMarch (k_refine3), RefineScan (k_best3), Eval (k_sdf_eval3: rays = [P, 3] points)
+int ring3_launch(const nrt_sdf* s, Pass pass, const float* rays, int64_t P, const MarchArgs& ma,
+                 const MarchOut& out, hipStream_t st);
 // NRT_MIXED intersect (nrt_ring_mixed.hip): FP16 march + scan, split refinement of the
 // undecidable steps and scan orders, split sdf(best); same outputs as ring_march
 // The FP16 SDF error of the headline scene (tools/fp16_decompose.py, 1M scan points and the

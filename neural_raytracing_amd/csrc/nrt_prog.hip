@@ -104,21 +104,6 @@ int build_bsdf_program(nrt_bsdf* b) {
 
 namespace {
 constexpr int kShadeWaves = 8;
-
-template <class K>
-int persistent_blocks(K kern, int threads, size_t lds, int64_t want) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  }
-  int per_cu = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern),
-                                                   threads, lds) != hipSuccess || per_cu < 1)
-    per_cu = 1;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * per_cu));
-}
 }  // namespace
 
 // NRT_EUNSUPPORTED when the program path does not cover this light / BSDF pair
@@ -139,13 +124,13 @@ int shade_program(const nrt_bsdf* b, const nrt_light* l, const float* p, const f
       auto kern = k_light16<WV, true>;
       const size_t lds = ring::KEngine<WV>::lds_bytes(l->prog.d);
       if (!(rc = set_lds(kern, lds))) {
-        kern<<<dim3(persistent_blocks(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
+        kern<<<dim3(resident_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
             l->prog.d, l->dev, p, n, wi, hit_idx, hit_count, lscale, ls);
         rc = check_launch("k_light16");
       }
     } else {
       auto kern = k_light16<WV, false>;
-      kern<<<dim3(persistent_blocks(kern, 64 * WV, 0, want)), dim3(64 * WV), 0, st>>>(
+      kern<<<dim3(resident_grid(kern, 64 * WV, 0, want)), dim3(64 * WV), 0, st>>>(
           l->prog.d, l->dev, p, n, wi, hit_idx, hit_count, lscale, ls);
       rc = check_launch("k_light16");
     }
@@ -156,7 +141,7 @@ int shade_program(const nrt_bsdf* b, const nrt_light* l, const float* p, const f
     const size_t lds = ring::KEngine<WV>::lds_bytes(b->prog.d) + (size_t)WV * 32 * kMaxComponents * 4;
     auto launch = [&](auto kern) {
       if ((rc = set_lds(kern, lds))) return;
-      kern<<<dim3(persistent_blocks(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
+      kern<<<dim3(resident_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
           b->prog.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out, n, pdf_out);
       rc = check_launch("k_bsdf16");
     };

@@ -37,7 +37,7 @@ int ring_march_mixed(const nrt_sdf* s, const float* rays, int64_t P, const March
   auto* list = reinterpret_cast<int32_t*>(ws + 2 * k8);
   auto* lcount = reinterpret_cast<int32_t*>(ws + 2 * k8 + (((size_t)P * 4 + 255) & ~(size_t)255));
   const float rd = 1e-7f * (float)option(OPT_MIXED_D), rs = 1e-7f * (float)option(OPT_MIXED_S);
-  if (scan) {
+  if (scan) {  // (the entry clears the scan keys, once: nrt_launch.h)
     NRT_HIP(hipMemsetAsync(keys, 0xff, (size_t)P * 8, st));
     NRT_HIP(hipMemsetAsync(keys2, 0xff, (size_t)P * 8, st));
   }
@@ -52,7 +52,8 @@ int ring_march_mixed(const nrt_sdf* s, const float* rays, int64_t P, const March
   m16.zone = restart == 2 ? 1e-7f * (float)option(OPT_MIXED_ZONE) : 0.f;
   m16.amb = amb;
   m16.keys2 = scan ? keys2 : nullptr;
-  if (int rc = ring_march16_launch(s, rays, P, m16, t, thr, keys, st, false)) return rc;
+  if (int rc = ring16_launch(s, Pass::RefineMarch, rays, P, m16, {.t = t, .thr = thr, .keys = keys}, st))
+    return rc;
   // 2. the flagged rays, resumed on the split engine
   k_refine_list<><<<dim3(std::min<int64_t>(ceil_div64(P, 256), 2048)), dim3(256), 0, st>>>(
       amb, P, list, lcount);
@@ -67,7 +68,7 @@ int ring_march_mixed(const nrt_sdf* s, const float* rays, int64_t P, const March
   // option "mixed_restart" (default): a flagged ray marches again from t = 0 -- resumed at the
   // flagged step instead, it would carry the FP16 march's drift of t into the decision
   mr.start = restart == 1 ? nullptr : amb;
-  if (int rc = ring3_launch(s, rays, P, mr, t, nullptr, nullptr, st, 2)) return rc;
+  if (int rc = ring3_launch(s, Pass::RefineMarch, rays, P, mr, {.t = t}, st)) return rc;
   // 3. sdf(best) at FP32 accuracy, over both candidates where FP16 could not order them
   if (scan) {
     auto* kbest = amb;  // the march flags are spent
@@ -76,14 +77,12 @@ int ring_march_mixed(const nrt_sdf* s, const float* rays, int64_t P, const March
     mb.keys2 = keys2;
     mb.kbest = kbest;
     mb.refine_s = rs;
-    if (int rc = ring3_launch(s, rays, P, mb, nullptr, thr, keys, st, 3)) return rc;
+    if (int rc = ring3_launch(s, Pass::RefineScan, rays, P, mb, {.thr = thr, .keys = keys}, st)) return rc;
     k_scan_pick<><<<dim3(ceil_div64(P, 256)), dim3(256), 0, st>>>(kbest, P, keys, thr);
     if (int rc = check_launch("k_scan_pick")) return rc;
   }
   // 4. unpack
-  k_march_finish<><<<dim3(std::min<int64_t>(ceil_div64(P, 256), 2048)), dim3(256), 0, st>>>(
-      rays, P, t, hit, p, n, raw_n, idx, cnt);
-  return check_launch("k_march_finish");
+  return march_finish(rays, P, t, hit, p, n, raw_n, idx, cnt, st);
 }
 
 }  // namespace nrt

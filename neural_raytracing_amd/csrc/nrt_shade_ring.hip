@@ -329,33 +329,12 @@ int build_rprog(const std::vector<const nrt_mlp*>& mlps, bool split, nrt_rprog& 
 namespace {
 constexpr int kRWaves = 8;
 
-template <class K>
-int persistent_grid(K kern, int threads, size_t lds, int64_t want) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-  }
-  int per_cu = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern),
-                                                   threads, lds) != hipSuccess || per_cu < 1)
-    per_cu = 1;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * per_cu));
-}
-
 // ring depth: 3 slots where they fit beside the tables in the CU's LDS, else 2
 template <int PREC, int WV, class F>
 int with_depth(const RProgDev& d, F&& f) {
   if (rprog::Engine<3, WV>::lds_bytes(d) <= (size_t)kLdsBytes) return f(std::integral_constant<int, 3>{});
   if (rprog::Engine<2, WV>::lds_bytes(d) <= (size_t)kLdsBytes) return f(std::integral_constant<int, 2>{});
   return NRT_EUNSUPPORTED;
-}
-
-int blocks_per_cu(const void* kern, int threads, size_t lds) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess) return 1;
-  return std::max(per_cu, 1);
 }
 
 // as with_depth, but 2 slots where that keeps more blocks resident on a CU (a kernel with few
@@ -368,8 +347,7 @@ int with_depth_occ(const RProgDev& d, KF&& kern_of, F&& f) {
   const size_t l3 = rprog::Engine<3, WV>::lds_bytes(d), l2 = rprog::Engine<2, WV>::lds_bytes(d);
   if (l3 <= (size_t)kLdsBytes) {
     if (l2 <= (size_t)kLdsBytes &&
-        blocks_per_cu(reinterpret_cast<const void*>(kern_of(D2{})), 64 * WV, l2) >
-            blocks_per_cu(reinterpret_cast<const void*>(kern_of(D3{})), 64 * WV, l3))
+        blocks_per_cu(kern_of(D2{}), 64 * WV, l2) > blocks_per_cu(kern_of(D3{}), 64 * WV, l3))
       return f(D2{});
     return f(D3{});
   }
@@ -429,13 +407,13 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
           auto kern = rprog::k_light_r<PREC, D, WV>;
           const size_t lds = rprog::Engine<D, WV>::lds_bytes(lp.d);
           if (int r = set_lds(kern, lds)) return r;
-          kern<<<dim3(persistent_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
+          kern<<<dim3(resident_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
               lp.d, l->dev, p, n, wi, hit_idx, hit_count, lscale, ls);
           return check_launch("k_light_r");
         });
       } else {
         auto kern = k_light16<WV, false>;  // point light: VALU only, FP32 math
-        kern<<<dim3(persistent_grid(kern, 64 * WV, 0, ceil_div64(P, 32 * WV))), dim3(64 * WV), 0, st>>>(
+        kern<<<dim3(resident_grid(kern, 64 * WV, 0, ceil_div64(P, 32 * WV))), dim3(64 * WV), 0, st>>>(
             ProgDev{}, l->dev, p, n, wi, hit_idx, hit_count, lscale, ls);
         rc = check_launch("k_light16");
       }
@@ -448,7 +426,7 @@ int shade_ring(const nrt_bsdf* b, const nrt_light* l, const float* p, const floa
       const size_t lds = rprog::Engine<D, WV>::lds_bytes(bp.d);
       auto launch = [&](auto kern) -> int {
         if (int r = set_lds(kern, lds)) return r;
-        kern<<<dim3(persistent_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
+        kern<<<dim3(resident_grid(kern, 64 * WV, lds, want)), dim3(64 * WV), lds, st>>>(
             bp.d, b->dev, p, wi, hit_idx, hit_count, ls, rgb, weights_out, n, pdf_out);
         return check_launch("k_bsdf_r");
       };
@@ -577,7 +555,7 @@ int ring_backward(const nrt_mlp* const* mlps, int n, const float* x, int64_t M,
         auto kern = rprog::k_mlp_bwd_ring<D, WV, S, SV>;
         const size_t lds = rprog::Engine<D, WV>::lds_bytes(d0);
         if (int r = set_lds(kern, lds)) return r;
-        kern<<<dim3(persistent_grid(kern, 64 * WV, lds, want), n), dim3(64 * WV), lds, st>>>(tj, x, M);
+        kern<<<dim3(resident_grid(kern, 64 * WV, lds, want), n), dim3(64 * WV), lds, st>>>(tj, x, M);
         return check_launch("k_mlp_bwd_ring");
       });
     };
@@ -634,7 +612,7 @@ int solo_forward_multi(const nrt_mlp* const* mlps, int n, const float* x, int64_
         const size_t lds = rprog::Engine<D, WV>::lds_bytes(d0);
         if (int r = set_lds(kern, lds)) return r;
         ProfScope prof("k_mlp_ring32", st);
-        kern<<<dim3(persistent_grid(kern, 64 * WV, lds, want), n), dim3(64 * WV), lds, st>>>(jobs, x, M);
+        kern<<<dim3(resident_grid(kern, 64 * WV, lds, want), n), dim3(64 * WV), lds, st>>>(jobs, x, M);
         return check_launch("k_mlp_ring32");
       });
     };
