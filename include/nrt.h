@@ -600,6 +600,70 @@ int nrt_plain_nerf_forward(const nrt_mlp* first, const nrt_mlp* second, const fl
 int nrt_light_envmap(const nrt_light* light, int32_t bins, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Volume-rendering training path of PlainNeRF and NeRFLE (torch autograd
+ * through nerf.py:46-74 / :175-214): the steps between and after the two MLPs, forward and
+ * backward.  The caller runs the MLPs (nrt_mlp_forward / nrt_mlp_backward) between them.
+ * Samples are sample-major, i = s * P + p, n = S * P.  `model` selects the shapes and the
+ * colour map.  Every call is stream-ordered and overwrites its outputs (nothing accumulates);
+ * none uses float atomics, so the same inputs give the same bits on every run.
+ *   NRT_NERF_NERFLE  first_out [n, 65], second input x2 [n, 67 + LK] = [latent 64 | r_d | light],
+ *                    sigmoid colours, out = sum_s w_s rgb_s            (nerf.py:199-214)
+ *   NRT_NERF_PLAIN   first_out [n, 1 + I], second input x2 [n, 2] = dir_to_elev_azim(r_d) and
+ *                    latent lat2 [n, I + L] = [intermediate | latent row p / rays_per_latent],
+ *                    sigma from alpha + noise, tanh colours, out = (sum_s w_s rgb_s + 1) / 2
+ *                                                                      (nerf.py:52-74)
+ * ------------------------------------------------------------------------------------- */
+#define NRT_NERF_NERFLE 0
+#define NRT_NERF_PLAIN 1
+
+/* Workspace of nrt_nerf_composite_backward and nrt_nerf_reduce for P rays, S samples and
+ * reductions of up to `dim` columns (the calls of one chunk may share one workspace). */
+size_t nrt_nerf_volume_workspace_bytes(int64_t P, int32_t S, int32_t dim);
+/* pts [n, 3] = r_o + ts[s] r_d (nerf.py:51, :179) and, for NRT_NERF_PLAIN, the first MLP's
+ * latent rows lat1 [n, L] (nerf.py:52; latent [rows, L], ray p reads row p / rays_per_latent).
+ * NRT_NERF_NERFLE ignores latent, L, rays_per_latent and lat1. */
+int nrt_nerf_points(int32_t model, const float* rays, int64_t P, const float* ts, int32_t S,
+                    const float* latent, int32_t L, int64_t rays_per_latent, float* pts,
+                    float* lat1, void* stream);
+/* The second MLP's inputs from first_out, each first_out row read once (nerf.py:57-63,
+ * :181-202), and the compact alpha_raw [S, P] = first_out[:, 0] (+ noise [S, P] for
+ * NRT_NERF_PLAIN, nerf.py:65-67; NULL: none).  extra: NERFLE's light encoding [extra_dim] or
+ * PLAIN's latent [rows, extra_dim].  NERFLE ignores I, rays_per_latent, noise and lat2. */
+int nrt_nerf_assemble(int32_t model, const float* first_out, const float* rays, int64_t P,
+                      int32_t S, const float* extra, int32_t extra_dim, int32_t I,
+                      int64_t rays_per_latent, const float* noise, float* x2, float* lat2,
+                      float* alpha_raw, void* stream);
+/* Backward of nrt_nerf_assemble into whole rows d_first_out [n, 65 | 1 + I]: column 0 from
+ * d_alpha_raw [S, P], columns 1.. from the leading columns of d_second -- the second MLP's
+ * dx [n, 67 + extra_dim] (NERFLE: torch.cat's gradient, nerf.py:199-203) or its dlatent
+ * [n, I + extra_dim] (PLAIN, nerf.py:63). */
+int nrt_nerf_assemble_backward(int32_t model, const float* d_alpha_raw, const float* d_second,
+                               int64_t P, int32_t S, int32_t extra_dim, int32_t I,
+                               float* d_first_out, void* stream);
+/* The reference's compositing (nerf.py:64-74, :203-214) from alpha_raw [S, P] and the second
+ * MLP's output rgb_raw [n, 3]: sigma = relu(alpha_raw), a = 1 - exp(-sigma ts[s]), the rolled
+ * cumprod of clamp(1 - a, 1e-10) with its last entry 1, out [P, 3].  Bit-equal to the frame of
+ * nrt_nerfle_forward / nrt_plain_nerf_forward (FP32 parity path) on the same MLP outputs. */
+int nrt_nerf_composite_forward(int32_t model, const float* alpha_raw, const float* rgb_raw,
+                               const float* ts, int64_t P, int32_t S, float* out, void* stream);
+/* Its backward: d_out [P, 3] -> d_alpha_raw [S, P], d_rgb_raw [n, 3] (the gradients of relu,
+ * exp, clamp, cumprod, roll and the colour map; one reverse recursion per ray, no division by
+ * the clamped transmittance). */
+int nrt_nerf_composite_backward(int32_t model, const float* alpha_raw, const float* rgb_raw,
+                                const float* ts, int64_t P, int32_t S, const float* d_out,
+                                float* d_alpha_raw, float* d_rgb_raw, void* workspace,
+                                void* stream);
+/* The gradients of the inputs every sample shares, summed in two stages in a fixed order:
+ *   NERFLE  out [dim] = sum_i d_second[i, 67:]  (d_second = the second MLP's dx [n, 67 + dim]:
+ *           the expanded light encoding, nerf.py:193-197; d_first unused)
+ *   PLAIN   out [P / rays_per_latent, dim] = per latent row, the sum over its rays' samples of
+ *           d_first[i, :] + d_second[i, I:]  (the MLPs' dlatent [n, dim], [n, I + dim]: the
+ *           expanded latent, nerf.py:52, :63); P a multiple of rays_per_latent. */
+int nrt_nerf_reduce(int32_t model, const float* d_first, const float* d_second, int64_t P,
+                    int32_t S, int32_t dim, int32_t I, int64_t rays_per_latent, float* out,
+                    void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Kernel timing (bench / profiling aid; no reference counterpart)
  * When enabled, the heavy launches (k_intersect, k_sdf_grad, k_shade_direct, k_mlp_forward)
  * are bracketed by hipEvents on the stream they run on.  nrt_profile_read synchronises those

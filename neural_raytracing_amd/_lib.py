@@ -26,6 +26,7 @@ NRT_BSDF_NEURAL, NRT_BSDF_DIFFUSE, NRT_BSDF_CONDUCTOR = 0, 1, 2
 NRT_BSDF_PHONG, NRT_BSDF_PLASTIC = 3, 4
 NRT_BSDF_PARAMS = 12
 NRT_CAM_NERF, NRT_CAM_DTU, NRT_CAM_FOV = 0, 1, 2
+NRT_NERF_NERFLE, NRT_NERF_PLAIN = 0, 1
 
 
 class NrtError(RuntimeError):
@@ -139,6 +140,14 @@ _SIGNATURES = {
     "nrt_light_envmap": (_I32, [_P, _I32, _P, _P]),
     "nrt_plain_nerf_workspace_bytes": (ctypes.c_size_t, [_P, _P, _I64, _I32]),
     "nrt_plain_nerf_forward": (_I32, [_P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I32, _P]),
+    "nrt_nerf_volume_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),
+    "nrt_nerf_points": (_I32, [_I32, _P, _I64, _P, _I32, _P, _I32, _I64, _P, _P, _P]),
+    "nrt_nerf_assemble": (_I32, [_I32, _P, _P, _I64, _I32, _P, _I32, _I32, _I64, _P, _P, _P, _P,
+                                 _P]),
+    "nrt_nerf_assemble_backward": (_I32, [_I32, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
+    "nrt_nerf_composite_forward": (_I32, [_I32, _P, _P, _P, _I64, _I32, _P, _P]),
+    "nrt_nerf_composite_backward": (_I32, [_I32, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "nrt_nerf_reduce": (_I32, [_I32, _P, _P, _I64, _I32, _I32, _I32, _I64, _P, _P, _P]),
     "nrt_mlp_backward_workspace_bytes": (ctypes.c_size_t, [_P, _I64]),
     "nrt_mlp_backward": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "nrt_mlp_backward_multi_workspace_bytes": (ctypes.c_size_t, [_P, _I32, _I64]),

@@ -183,6 +183,23 @@ __global__ void k_plain_first_in(const float* __restrict__ rays, int64_t P,
   }
 }
 
+// the sample-point launches, shared with the training path (nrt_nerf_train.hip)
+int launch_nerf_points(const float* rays, int64_t P, const float* ts, int S, float* pts,
+                       hipStream_t st) {
+  const int blocks = (int)std::min<int64_t>(ceil_div64(P * (int64_t)S, 256), 4096);
+  k_nerf_points<><<<dim3(blocks), dim3(256), 0, st>>>(rays, P, ts, S, pts);
+  return check_launch("k_nerf_points");
+}
+
+int launch_plain_first_in(const float* rays, int64_t P, const float* ts, int S,
+                          const float* latent, int L, int64_t rays_per_latent, float* pts,
+                          float* lat1, hipStream_t st) {
+  const int blocks = (int)std::min<int64_t>(ceil_div64(P * (int64_t)S, 256), 4096);
+  k_plain_first_in<><<<dim3(blocks), dim3(256), 0, st>>>(rays, P, ts, S, latent, L,
+                                                          rays_per_latent, pts, lat1);
+  return check_launch("k_plain_first_in");
+}
+
 // second MLP input: x = dir_to_elev_azim(r_d) (utils.py:490-494), latent = [intermediate, latent]
 // (nerf.py:60-64; first_out = [alpha | intermediate (I)])
 template <int = 0>

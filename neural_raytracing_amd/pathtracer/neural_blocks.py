@@ -175,6 +175,52 @@ def _live_rows(dys, M):
     return None if idx.numel() > (1.0 - COMPACT_MIN_DEAD) * M else idx
 
 
+def mlp_first_order(mlp, handle, save, x, lat, dy, want_dx, want_dlat):
+    """One MLP backward on the packed weights of ``handle``: (dL/dx, dL/dlatent, [dW0, db0, dW1,
+    ...]) from nrt_mlp_backward_saved when the forward saved its activations (``save``, from
+    _forward_saving), else nrt_mlp_backward.  Shared by _MlpFn and the fused volume render."""
+    import ctypes
+    lib = _lib.load(require_device=True)
+    M = x.shape[0]
+    dy = dy.detach().float().contiguous()
+    lins = mlp._linears()
+    idx = _live_rows([dy], M)
+    if idx is not None:  # the rows with a gradient only (COMPACT_MIN_DEAD)
+        full_x, full_lat = x, lat
+        x, dy = x[idx].contiguous(), dy[idx].contiguous()
+        lat = None if lat is None else lat[idx].contiguous()
+        M = x.shape[0]
+    dx = torch.empty_like(x) if want_dx else None
+    dlat = torch.empty_like(lat) if (lat is not None and want_dlat) else None
+    zeros = M == 0
+    mk = torch.zeros_like if zeros else torch.empty_like
+    dws = [mk(lin.weight) if lin.weight.requires_grad else None for lin in lins]
+    dbs = [mk(lin.bias) if lin.bias.requires_grad else None for lin in lins]
+    wp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dws])
+    bp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dbs])
+    if not zeros and save is not None:  # the forward saved the activations
+        P = ctypes.c_void_p
+        ws = torch.empty(lib.nrt_mlp_backward_multi_workspace_bytes((P * 1)(handle.value), 1, M),
+                         dtype=torch.uint8, device=x.device)
+        rows = None if idx is None else idx.to(torch.int32)
+        _lib.call("nrt_mlp_backward_saved", (P * 1)(handle.value), 1, _lib.ptr(x), M,
+                  _lib.ptr(rows), (P * 1)(save[0].data_ptr()), full_x.shape[0] if idx is not None else M,
+                  (P * 1)(dy.data_ptr()), None if dx is None else (P * 1)(dx.data_ptr()),
+                  wp, bp, _lib.ptr(ws), _lib.stream())
+    elif not zeros:
+        ws = torch.empty(lib.nrt_mlp_backward_workspace_bytes(handle.value, M),
+                         dtype=torch.uint8, device=x.device)
+        _lib.call("nrt_mlp_backward", handle.value, _lib.ptr(x), _lib.ptr(lat), M,
+                  _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dlat), wp, bp, _lib.ptr(ws),
+                  _lib.stream())
+    if idx is not None:  # scatter back: dL/dx = 0 on the rows without a gradient
+        if dx is not None:
+            dx = torch.zeros_like(full_x).index_copy_(0, idx, dx)
+        if dlat is not None:
+            dlat = torch.zeros_like(full_lat).index_copy_(0, idx, dlat)
+    return dx, dlat, [g for pair in zip(dws, dbs) for g in pair]
+
+
 class _MlpFn(torch.autograd.Function):
     """y = SkipConnMLP(x, latent) with gradients for x, latent and every nn.Linear weight and
     bias from nrt_mlp_backward.  basis_p is a plain tensor attribute in the
@@ -209,50 +255,10 @@ class _MlpFn(torch.autograd.Function):
     @staticmethod
     def _first_order(ctx, dy):
         """dL/dx, dL/dlatent and the nn.Linear gradients from nrt_mlp_backward (no graph)."""
-        import ctypes
         x, lat = ctx.saved_tensors
-        x = x.detach()
-        lat = lat.detach() if ctx.has_lat else None
-        mlp = ctx.mlp
-        lib = _lib.load(require_device=True)
-        M = x.shape[0]
-        dy = dy.detach().float().contiguous()
-        lins = mlp._linears()
-        idx = _live_rows([dy], M)
-        if idx is not None:  # the rows with a gradient only (COMPACT_MIN_DEAD)
-            full_x, full_lat = x, lat
-            x, dy = x[idx].contiguous(), dy[idx].contiguous()
-            lat = None if lat is None else lat[idx].contiguous()
-            M = x.shape[0]
-        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        dlat = torch.empty_like(lat) if (lat is not None and ctx.needs_input_grad[2]) else None
-        zeros = M == 0
-        mk = torch.zeros_like if zeros else torch.empty_like
-        dws = [mk(lin.weight) if lin.weight.requires_grad else None for lin in lins]
-        dbs = [mk(lin.bias) if lin.bias.requires_grad else None for lin in lins]
-        wp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dws])
-        bp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dbs])
-        if not zeros and ctx.save is not None:  # the forward saved the activations
-            P = ctypes.c_void_p
-            ws = torch.empty(lib.nrt_mlp_backward_multi_workspace_bytes((P * 1)(ctx.handle.value), 1, M),
-                             dtype=torch.uint8, device=x.device)
-            rows = None if idx is None else idx.to(torch.int32)
-            _lib.call("nrt_mlp_backward_saved", (P * 1)(ctx.handle.value), 1, _lib.ptr(x), M,
-                      _lib.ptr(rows), (P * 1)(ctx.save[0].data_ptr()), full_x.shape[0] if idx is not None else M,
-                      (P * 1)(dy.data_ptr()), None if dx is None else (P * 1)(dx.data_ptr()),
-                      wp, bp, _lib.ptr(ws), _lib.stream())
-        elif not zeros:
-            ws = torch.empty(lib.nrt_mlp_backward_workspace_bytes(ctx.handle.value, M),
-                             dtype=torch.uint8, device=x.device)
-            _lib.call("nrt_mlp_backward", ctx.handle.value, _lib.ptr(x), _lib.ptr(lat), M,
-                      _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dlat), wp, bp, _lib.ptr(ws),
-                      _lib.stream())
-        if idx is not None:  # scatter back: dL/dx = 0 on the rows without a gradient
-            if dx is not None:
-                dx = torch.zeros_like(full_x).index_copy_(0, idx, dx)
-            if dlat is not None:
-                dlat = torch.zeros_like(full_lat).index_copy_(0, idx, dlat)
-        return dx, dlat, [g for pair in zip(dws, dbs) for g in pair]
+        return mlp_first_order(ctx.mlp, ctx.handle, ctx.save, x.detach(),
+                               lat.detach() if ctx.has_lat else None, dy,
+                               ctx.needs_input_grad[1], ctx.needs_input_grad[2])
 
     @staticmethod
     def _backward_create_graph(ctx, dy):

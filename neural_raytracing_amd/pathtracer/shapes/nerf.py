@@ -1,6 +1,8 @@
 """Volumetric NeRF shapes (shapes/nerf.py).  ``NeRFLE`` (NeRF + point light, or NeRF + envmap
 light with envmap=True) renders through ``nrt_nerfle_forward``: sample points, both MLPs and the
-reference's compositing on the GPU.  Constructor and RNG consumption follow nerf.py:153-172."""
+reference's compositing on the GPU.  Constructor and RNG consumption follow nerf.py:153-172.
+With gradients, ``PlainNeRF`` (and ``NeRFLE`` when ``FUSED_TRAINING`` is set) renders through the
+one autograd Function of ``_volume``."""
 import random
 
 import torch
@@ -10,6 +12,7 @@ import torch.nn as nn
 from ... import _lib
 from ..differentiable import needs_grad
 from ..neural_blocks import SkipConnMLP
+from ._volume import VolumeSpec, render_volume
 
 
 class PlainNeRF(nn.Module):
@@ -20,6 +23,8 @@ class PlainNeRF(nn.Module):
     draws ``random.random()`` for ``ts = linspace(0.4, 2 + r*0.1, steps)`` and the density noise
     ``randn * 1e-3`` per sample (nerf.py:50, :66; on the device, ``noise=`` injects it) and
     returns ``(rgb + 1) / 2`` with the reference's compositing.  ``lights`` is unused, as there.
+    When a parameter or the latent takes a gradient the same render runs as one autograd
+    Function (``_volume._VolumeFn``) in chunks of the same bound.
     """
 
     MAX_SAMPLES_PER_CALL = 1 << 22
@@ -45,9 +50,7 @@ class PlainNeRF(nn.Module):
         if not rays.is_cuda:
             raise _lib.NrtError("PlainNeRF renders on the HIP path only: move it and the rays to "
                                 "the GPU")
-        if needs_grad(self) or (torch.is_grad_enabled() and self.latent.requires_grad):
-            raise _lib.NrtError("PlainNeRF is not on the HIP training path: render it under "
-                                "torch.no_grad()")
+        train = needs_grad(self) or (torch.is_grad_enabled() and self.latent.requires_grad)
         lead = rays.shape[:-1]
         if len(lead) < 2 or lead[0] != self.latent.shape[0]:
             raise _lib.NrtError(f"PlainNeRF: rays {tuple(rays.shape)} must be [N, ..., 6] with "
@@ -60,8 +63,14 @@ class PlainNeRF(nn.Module):
         if noise is None:
             noise = torch.randn(S, P, device=dev) * 1e-3
         noise = noise.reshape(S, P).float().contiguous()
-        latent = self.latent.detach().float().to(dev).contiguous()
         per = P // lead[0]
+        if train and P > 0:
+            # autograd through the whole render: _VolumeFn (both MLPs, the latent)
+            spec = VolumeSpec(_lib.NRT_NERF_PLAIN, self.first, self.second, S, per,
+                              self.MAX_SAMPLES_PER_CALL // S)
+            rgb = render_volume(spec, flat, ts, self.latent.float().to(dev), noise.detach())
+            return rgb.reshape(lead + (3,))
+        latent = self.latent.detach().float().to(dev).contiguous()
         lib = _lib.load(require_device=True)
         rgb = torch.empty(P, 3, device=dev)
         # bounded intermediates: chunks of whole cameras, or pieces of one camera's rays (the
@@ -100,6 +109,12 @@ class NeRFLE(nn.Module):
     # intermediates (~564 B a sample: 4M samples), the fused FP16 kernel 16 B a sample (134M
     # samples: cfg5's 1600^2 x 256 frame in 5 calls instead of 157)
     MAX_WORKSPACE_BYTES = 1 << 31
+    # True: the gradient branch of forward runs the fused volume render (_VolumeFn: points,
+    # assembly, compositing and their backwards in HIP, chunks of MAX_SAMPLES_PER_CALL samples)
+    # instead of the tensor-op chain of _forward_train; off until the step times decide
+    # ("Volume-rendering training path")
+    FUSED_TRAINING = False
+    MAX_SAMPLES_PER_CALL = 1 << 22
 
     def __init__(self, envmap=False, bins=4, device="cuda", steps=64):
         super().__init__()
@@ -135,6 +150,10 @@ class NeRFLE(nn.Module):
                 light = lights.envmap(elev_azim_to_dir(points)).reshape(-1).float()
             else:
                 light = lights.location.reshape(-1, 3)[0].detach().float().to(dev)
+            if self.FUSED_TRAINING and P > 0:
+                spec = VolumeSpec(_lib.NRT_NERF_NERFLE, self.first, self.second, self.steps, P,
+                                  self.MAX_SAMPLES_PER_CALL // self.steps)
+                return render_volume(spec, flat, ts, light).reshape(lead + (3,))
             return self._forward_train(flat, ts, light).reshape(lead + (3,))
         lib = _lib.load(require_device=True)
         if getattr(self, "envmap", False):
