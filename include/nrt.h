@@ -118,7 +118,9 @@ size_t nrt_mlp_save_bytes(const nrt_mlp* mlp, int64_t M);
  *   dweights[l] [R_l, C_l] and dbiases[l] [R_l] for l = 0 (init), 1..num_layers (hidden),
  *   num_layers + 1 (out), in the torch nn.Linear layouts (host arrays of device pointers; the
  *   arrays or single entries may be NULL).  Gradients are overwritten, not accumulated.
- * workspace: nrt_mlp_backward_workspace_bytes(mlp, M) bytes of device memory. */
+ * workspace: nrt_mlp_backward_workspace_bytes(mlp, M) bytes of device memory, which is
+ * nrt_mlp_backward_multi_workspace_bytes(&mlp, 1, M): the call is nrt_mlp_backward_multi with one
+ * MLP (same results bit for bit), which alone may carry a latent. */
 size_t nrt_mlp_backward_workspace_bytes(const nrt_mlp* mlp, int64_t M);
 int nrt_mlp_backward(const nrt_mlp* mlp, const float* x, const float* latent, int64_t M,
                      const float* dy, float* dx, float* dlatent, float* const* dweights,
@@ -129,7 +131,8 @@ int nrt_mlp_backward(const nrt_mlp* mlp, const float* x, const float* latent, in
  * (bsdfs.py:634-637) -- in one backward launch and one weight-gradient launch.  dy[i] [M, out],
  * dx[i] [M, in] (the array or entries may be NULL); dweights / dbiases are flat host arrays of
  * n x (num_layers + 2) device pointers, MLP-major.  Per MLP the same results as nrt_mlp_backward
- * up to the split-K summation order of the weight gradients.
+ * up to the split-K summation order of the weight gradients (the slice count follows from all n
+ * MLPs' jobs; n == 1 is bit-equal).
  * workspace: nrt_mlp_backward_multi_workspace_bytes(mlps, n, M) bytes. */
 size_t nrt_mlp_backward_multi_workspace_bytes(const nrt_mlp* const* mlps, int n, int64_t M);
 int nrt_mlp_backward_multi(const nrt_mlp* const* mlps, int n, const float* x, int64_t M,

@@ -519,41 +519,16 @@ __device__ __forceinline__ void mlp_backward_cs(
     for (int j = h + 2 * w; j < m.latent; j += 2 * CW) dLat[row * m.latent + j] = egrad[es * (2 * F + in + j)];
 }
 
-template <int NB, bool TILE>
-__global__ void __launch_bounds__(64 * ColSplit<NB>::CW, 2) k_mlp_backward32_cs(
-    const MlpDev* __restrict__ mp, const float* __restrict__ x, const float* __restrict__ lat,
-    int64_t M, const float* __restrict__ dY, float* __restrict__ dX, float* __restrict__ dLat,
-    float* __restrict__ Zg, float* __restrict__ Ag, float* __restrict__ Eraw,
-    float* __restrict__ Eact, float* __restrict__ dZg, float* __restrict__ Et,
-    float* __restrict__ Gt, int RS) {
-  mlp_backward_cs<NB, TILE>(mp, x, lat, M, dY, dX, dLat, Zg, Ag, Eraw, Eact, dZg, Et, Gt, RS);
-}
-
-struct BwdJob;
-template <int NB, bool TILE>
-__global__ void __launch_bounds__(64 * ColSplit<NB>::CW, 2) k_mlp_backward32_multi_cs(
-    const BwdJob* __restrict__ jobs, const float* __restrict__ x, int64_t M, int RS);
-
-// below four row blocks two waves per SIMD fit (registers and slab): ask the compiler for that
-template <int NB, bool TILE>
-__global__ void __launch_bounds__(256, NB <= 4 ? 2 : 1) k_mlp_backward32(
-    const MlpDev* __restrict__ mp, const float* __restrict__ x, const float* __restrict__ lat,
-    int64_t M, const float* __restrict__ dY, float* __restrict__ dX, float* __restrict__ dLat,
-    float* __restrict__ Zg, float* __restrict__ Ag, float* __restrict__ Eraw,
-    float* __restrict__ Eact, float* __restrict__ dZg, float* __restrict__ Et,
-    float* __restrict__ Gt, int RS, int per_wave) {
-  mlp_backward32<NB, TILE>(mp, x, lat, M, dY, dX, dLat, Zg, Ag, Eraw, Eact, dZg, Et, Gt, RS, per_wave);
-}
-
-// n same-shape MLPs on one input (the NeuralBSDFs of a spatially varying mixture all read the
-// same Rusinkiewicz features): one launch, blockIdx.y = MLP.  Each MLP alone is 1,200 32-row waves
-// on 1,024 SIMDs for a 38,400-ray training batch; together they fill the machine.
+// One launch for n same-shape MLPs on one input (blockIdx.y = MLP): the NeuralBSDFs of a spatially
+// varying mixture all read the same Rusinkiewicz features, and each alone is 1,200 32-row waves on
+// 1,024 SIMDs for a 38,400-ray training batch; together they fill the machine.
 struct BwdJob {
   const MlpDev* mp;
   const float* dY;
   float *dX, *Z, *A, *Eraw, *Eact, *dZ, *Et, *Gt;
 };
 
+// below four row blocks two waves per SIMD fit (registers and slab): ask the compiler for that
 template <int NB, bool TILE>
 __global__ void __launch_bounds__(256, NB <= 4 ? 2 : 1) k_mlp_backward32_multi(
     const BwdJob* __restrict__ jobs, const float* __restrict__ x, int64_t M, int RS, int per_wave) {
@@ -568,6 +543,26 @@ __global__ void __launch_bounds__(64 * ColSplit<NB>::CW, 2) k_mlp_backward32_mul
   const BwdJob j = jobs[blockIdx.y];
   mlp_backward_cs<NB, TILE>(j.mp, x, nullptr, M, j.dY, j.dX, nullptr, j.Z, j.A, j.Eraw, j.Eact,
                             j.dZ, j.Et, j.Gt, RS);
+}
+
+// One MLP a call (nrt_mlp_backward; it alone may carry a latent): the job as a kernel argument,
+// no table copy.  These instances also need fewer VGPRs than the table's (119 against 154 for the
+// SDF shift's column-split kernel), and the latent read through the table cost the 128- and
+// 256-column per-wave kernels scratch and VGPR spills.
+template <int NB, bool TILE>
+__global__ void __launch_bounds__(256, NB <= 4 ? 2 : 1) k_mlp_backward32(
+    const BwdJob j, const float* __restrict__ x, const float* __restrict__ lat,
+    float* __restrict__ dLat, int64_t M, int RS, int per_wave) {
+  mlp_backward32<NB, TILE>(j.mp, x, lat, M, j.dY, j.dX, dLat, j.Z, j.A, j.Eraw, j.Eact, j.dZ,
+                           j.Et, j.Gt, RS, per_wave);
+}
+
+template <int NB, bool TILE>
+__global__ void __launch_bounds__(64 * ColSplit<NB>::CW, 2) k_mlp_backward32_cs(
+    const BwdJob j, const float* __restrict__ x, const float* __restrict__ lat,
+    float* __restrict__ dLat, int64_t M, int RS) {
+  mlp_backward_cs<NB, TILE>(j.mp, x, lat, M, j.dY, j.dX, dLat, j.Z, j.A, j.Eraw, j.Eact, j.dZ,
+                            j.Et, j.Gt, RS);
 }
 
 // second derivative of act at pre-activation x (torch double-backward formulas:
@@ -923,33 +918,6 @@ double grad_bwd_row_flop(const MlpDev& d) {
 }
 
 constexpr size_t kWgradTableBytes = 16384;  // device copy of a WgradBatch's job table
-
-struct TrainWs {
-  float *Z, *A, *dZ, *Eraw, *Eact, *Et, *Gt, *table, *part;
-};
-
-// per-wave encoding / encoding-gradient tiles of k_mlp_backward32: [waves][ke][32] floats
-static inline size_t enc_tile_bytes(const MlpDev& d, int64_t M) {
-  return (size_t)((M + 31) / 32) * 32 * (size_t)d.ke * 4;
-}
-
-TrainWs carve(const nrt_mlp* m, int64_t M, void* base) {
-  const MlpDev& d = m->host_dev;
-  const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
-  const size_t enc = (size_t)M * d.dp * 4;
-  char* p = (char*)base;
-  TrainWs w;
-  w.Z = (float*)p; p += a256(lay);
-  w.A = (float*)p; p += a256(lay);
-  w.dZ = (float*)p; p += a256(lay);
-  w.Eraw = (float*)p; p += a256(enc);
-  w.Eact = (float*)p; p += a256(enc);
-  w.Et = (float*)p; p += a256(enc_tile_bytes(d, M));
-  w.Gt = (float*)p; p += a256(enc_tile_bytes(d, M));
-  w.table = (float*)p; p += a256(kWgradTableBytes);  // weight-gradient job table
-  w.part = (float*)p;  // batched partial products
-  return w;
-}
 
 }  // namespace
 // (outside the anonymous namespace: the HIP runtime could not find k_wgrad's device symbol under
@@ -1410,18 +1378,46 @@ void backward_jobs(const MlpDev& d, bool grad_bwd, F&& f) {
   }
 }
 
-// the partial floats and slice count of every job of one MLP's backward (the workspace's plan)
-size_t batch_part_floats(const MlpDev& d, int64_t M, bool grad_bwd, int* slices = nullptr) {
-  WgradBatch b;
-  backward_jobs(d, grad_bwd, [&](int, int R, int kind, int C, int ldw, int c0) {
-    if (kind == 3) b.bias(nullptr, R, M, nullptr);
-    else b.weight(nullptr, R, nullptr, C, grad_bwd ? 2 * M : M, nullptr, ldw, c0);
+// where one MLP's weight-gradient operands lie: dZ [L+1][rows][H] (the out layer's is dY), the
+// layer inputs A [L+1][rows][H] and the encoding [rows][dp], raw (init layer) and activated (skip
+// layers)
+struct WgradSrc {
+  const float *dY, *dZ, *A, *Eraw, *Eact;
+};
+
+// One MLP's jobs into a batch: those whose gradient was requested, or (src null, the workspace's
+// plan) every job.  The double backward's weights run over the stacked 2M rows, its biases over
+// the M primal rows.
+void fill_wgrad(WgradBatch& b, const MlpDev& d, bool grad_bwd, int64_t M, const WgradSrc* src,
+                float* const* dweights, float* const* dbiases) {
+  const int L = d.n_hidden;
+  const int64_t Mw = grad_bwd ? 2 * M : M;
+  const size_t lay = (size_t)Mw * d.hidden;
+  backward_jobs(d, grad_bwd, [&](int l, int R, int kind, int C, int ldw, int c0) {
+    float* const* want = kind == 3 ? dbiases : dweights;
+    float* g = src && want ? want[l] : nullptr;
+    if (src && !g) return;  // not requested
+    const float* dZ = !src ? nullptr : l == L + 1 ? src->dY : src->dZ + (size_t)l * lay;
+    if (kind == 3) {
+      b.bias(dZ, R, M, g);
+      return;
+    }
+    const float* In = !src ? nullptr
+                    : kind == 0 ? src->Eraw
+                    : kind == 1 ? src->A + (size_t)(l - 1) * lay
+                                : src->Eact;
+    b.weight(dZ, R, In, C, Mw, g, ldw, c0);
   });
-  int S = 1;
-  const size_t floats = b.plan(S);
-  if (slices) *slices = S;
-  return floats;
 }
+
+// the partial floats and slice count of every job of n same-shape MLPs' backward: what the
+// workspace is sized with, and the slice count the launch then uses (WgradBatch::slices)
+size_t wgrad_part_floats(const MlpDev& d, int n, int64_t M, bool grad_bwd, int& slices) {
+  WgradBatch b;
+  for (int i = 0; i < n; ++i) fill_wgrad(b, d, grad_bwd, M, nullptr, nullptr, nullptr);
+  return b.plan(slices);
+}
+
 // k_mlp_backward32's LDS plan: slab row [hidden | encoding] (H + ke floats), or [hidden] with the
 // encoding in global tiles when that at least doubles the waves per CU (TILE)
 LdsPlan backward_plan(const MlpDev& d, bool& tile) {
@@ -1458,15 +1454,6 @@ LdsPlan backward_plan_cs(const MlpDev& d, bool& tile) {
   tile = (option(OPT_BWD_COLSPLIT) != 2 || per_cu(slab) < 2) && per_cu(tiled) >= 2 * per_cu(slab);
   return tile ? tiled : slab;
 }
-#define NRT_CW(NBv) (ColSplit<NBv>::CW)
-
-// one MLP's activations / gradients region of the multi-MLP workspace (carve's first seven arrays)
-size_t region_bytes(const MlpDev& d, int64_t M) {
-  const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
-  const size_t enc = (size_t)M * d.dp * 4;
-  return 3 * a256(lay) + 2 * a256(enc) + 2 * a256(enc_tile_bytes(d, M));
-}
-
 bool same_shape(const nrt_mlp* a, const nrt_mlp* b) {
   const MlpDev &x = a->host_dev, &y = b->host_dev;
   return x.hidden == y.hidden && x.n_hidden == y.n_hidden && x.ke == y.ke && x.dp == y.dp &&
@@ -1474,26 +1461,186 @@ bool same_shape(const nrt_mlp* a, const nrt_mlp* b) {
          x.latent == y.latent && x.nb == y.nb && a->desc.activation == b->desc.activation;
 }
 
-// the combined weight-gradient batch of n same-shape MLPs (pointers filled by the caller's f)
-template <class F>
-void multi_jobs(const MlpDev& d, int n, int64_t M, WgradBatch& b, F&& f) {
-  b.max_jobs = n * kMaxWgradJobs;
-  for (int i = 0; i < n; ++i)
-    backward_jobs(d, false, [&](int l, int R, int kind, int C, int ldw, int c0) { f(i, l, R, kind, C, ldw, c0); });
-  (void)M;
+// offsets of a workspace's 256-byte aligned arrays, in order
+struct Offsets {
+  size_t end = 0;
+  size_t take(size_t bytes) {
+    const size_t at = end;
+    end += a256(bytes);
+    return at;
+  }
+};
+
+// The first-order backward's workspace for n same-shape MLPs over M rows: n regions of seven
+// arrays (Z, A, dZ [L+1][M][H]; the encoding raw and activated [M][dp]; the TILE kernels' per-wave
+// encoding and encoding-gradient tiles [waves][ke][32]), the slab kernels' BwdJob table, one
+// weight-gradient job table per MLP (the ring backward's job table lies there too: the weight
+// gradients copy theirs after it ran) and the split-K partial products.
+struct TrainWs {
+  float *Z, *A, *dZ, *Eraw, *Eact, *Et, *Gt;
+};
+struct TrainLayout {
+  size_t Z, A, dZ, Eraw, Eact, Et, Gt, region;  // within one MLP's region; its bytes
+  size_t jobs, tables, part, bytes;
+  size_t part_floats;
+  int slices = 1;
+  TrainLayout(const MlpDev& d, int n, int64_t M) {
+    const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
+    const size_t enc = (size_t)M * d.dp * 4;
+    const size_t tile = (size_t)((M + 31) / 32) * 32 * (size_t)d.ke * 4;
+    Offsets r;
+    Z = r.take(lay); A = r.take(lay); dZ = r.take(lay);
+    Eraw = r.take(enc); Eact = r.take(enc);
+    Et = r.take(tile); Gt = r.take(tile);
+    region = r.end;
+    Offsets o;
+    o.take((size_t)n * region);
+    jobs = o.take((size_t)n * sizeof(BwdJob));
+    tables = o.take((size_t)n * kWgradTableBytes);
+    part_floats = wgrad_part_floats(d, n, M, false, slices);
+    part = o.take(part_floats * 4);
+    bytes = o.end;
+  }
+  TrainWs region_of(char* base, int i) const {
+    char* p = base + (size_t)i * region;
+    auto f = [&](size_t off) { return (float*)(p + off); };
+    return TrainWs{f(Z), f(A), f(dZ), f(Eraw), f(Eact), f(Et), f(Gt)};
+  }
+};
+
+// nrt_mlp_grad_backward's workspace: Z and its tangent T [L+1][M][H]; the activations A and the
+// gradients dZ over the stacked [primal; tangent] rows [L+1][2M][H]; the encoding E0 (raw |
+// tangent) and E1 (activated | its tangent) [2M][dp]; the out layer's seed [2M][out]; the
+// weight-gradient job table and the split-K partial products
+struct GradBwdLayout {
+  size_t Z, T, A, dZ, E0, E1, seed, table, part, bytes;
+  size_t part_floats;
+  int slices = 1;
+  GradBwdLayout(const MlpDev& d, int64_t M) {
+    const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
+    Offsets o;
+    Z = o.take(lay); T = o.take(lay); A = o.take(2 * lay); dZ = o.take(2 * lay);
+    E0 = o.take((size_t)2 * M * d.dp * 4); E1 = o.take((size_t)2 * M * d.dp * 4);
+    seed = o.take((size_t)2 * M * d.out * 4);
+    table = o.take(kWgradTableBytes);
+    part_floats = wgrad_part_floats(d, 1, M, true, slices);
+    part = o.take(part_floats * 4);
+    bytes = o.end;
+  }
+};
+
+// M == 0: every requested gradient of one MLP is zero
+int zero_grads(const nrt_mlp* m, float* const* dweights, float* const* dbiases, hipStream_t st) {
+  const MlpDev& d = m->host_dev;
+  for (int l = 0; l < d.n_hidden + 2; ++l) {
+    const int R = l == d.n_hidden + 1 ? d.out : d.hidden;
+    const int C = m->host_w[l].size() / (size_t)R;
+    if (dweights && dweights[l]) NRT_HIP(hipMemsetAsync(dweights[l], 0, (size_t)R * C * 4, st));
+    if (dbiases && dbiases[l]) NRT_HIP(hipMemsetAsync(dbiases[l], 0, (size_t)R * 4, st));
+  }
+  return NRT_OK;
 }
 
-// the partial floats and slice count of every job of n same-shape MLPs' backward
-size_t multi_part_floats(const MlpDev& d, int n, int64_t M, int* slices = nullptr) {
-  WgradBatch b;
-  multi_jobs(d, n, M, b, [&](int, int, int R, int kind, int C, int, int) {
-    if (kind == 3) b.bias(nullptr, R, M, nullptr);
-    else b.weight(nullptr, R, nullptr, C, M, nullptr, 0, 0);
+// the slab backward of n MLPs (blockIdx.y = MLP; their jobs copied to the device table tj): the
+// column-split or the per-wave kernel (option bwd_colsplit), the encoding in the slab or in global
+// tiles.  One MLP takes its job as a kernel argument.
+int launch_slab(const MlpDev& d, const BwdJob* jobs, int n, BwdJob* tj, const float* x,
+                const float* latent, float* dlatent, int64_t M, hipStream_t st) {
+  bool tile = false;
+  const bool cs = option(OPT_BWD_COLSPLIT) != 0;
+  const LdsPlan lp = cs ? backward_plan_cs(d, tile) : backward_plan(d, tile);
+  const int waves = ceil_div64(M, 32);
+  if (n > 1) NRT_HIP(hipMemcpyAsync(tj, jobs, (size_t)n * sizeof(BwdJob), hipMemcpyHostToDevice, st));
+  int rc = NRT_OK;
+  auto go = [&](auto solo, auto multi, dim3 grid, dim3 block, auto... per_wave) {
+    if (n == 1) {
+      if (!(rc = set_lds(solo, lp.bytes)))
+        solo<<<grid, block, lp.bytes, st>>>(jobs[0], x, latent, dlatent, M, lp.RS, per_wave...);
+    } else if (!(rc = set_lds(multi, lp.bytes))) {
+      multi<<<grid, block, lp.bytes, st>>>(tj, x, M, lp.RS, per_wave...);
+    }
+  };
+  NRT_NB_SWITCH(d.nb, {
+    const dim3 gcs(waves, n), bcs(64 * ColSplit<NB>::CW);
+    const dim3 grid(ceil_div64(waves, lp.waves), n), block(64 * lp.waves);
+    if (cs && tile) go(k_mlp_backward32_cs<NB, true>, k_mlp_backward32_multi_cs<NB, true>, gcs, bcs);
+    else if (cs) go(k_mlp_backward32_cs<NB, false>, k_mlp_backward32_multi_cs<NB, false>, gcs, bcs);
+    else if (tile) go(k_mlp_backward32<NB, true>, k_mlp_backward32_multi<NB, true>, grid, block, lp.per_wave);
+    else go(k_mlp_backward32<NB, false>, k_mlp_backward32_multi<NB, false>, grid, block, lp.per_wave);
   });
-  int S = 1;
-  const size_t floats = b.plan(S);
-  if (slices) *slices = S;
-  return floats;
+  return rc ? rc : check_launch("k_mlp_backward32");
+}
+
+// The first-order backward of n same-shape MLPs on one input, behind nrt_mlp_backward (n == 1,
+// the only case that may carry a latent), nrt_mlp_backward_multi and nrt_mlp_backward_saved
+// (saved: the training forward's activations, rows / Ms as ring_backward's; the ring backward
+// then runs the backward chain only).  dweights / dbiases: L + 2 pointers per MLP, or null.
+int backward_core(const nrt_mlp* const* mlps, int n, const float* x, const float* latent,
+                  int64_t M, const int32_t* rows, const void* const* saved, int64_t Ms,
+                  const float* const* dy, float* const* dx, float* dlatent,
+                  float* const* dweights, float* const* dbiases, void* workspace,
+                  hipStream_t st) {
+  const MlpDev& d = mlps[0]->host_dev;
+  const int NL = d.n_hidden + 2;
+  auto of = [&](float* const* g, int i) { return g ? g + (size_t)i * NL : nullptr; };
+  if (M == 0) {
+    for (int i = 0; i < n; ++i)
+      if (int rc = zero_grads(mlps[i], of(dweights, i), of(dbiases, i), st)) return rc;
+    return NRT_OK;
+  }
+  const TrainLayout lo(d, n, M);
+  char* base = (char*)workspace;
+  void* table = base + lo.tables;
+  std::vector<TrainWs> ws(n);
+  std::vector<WgradSrc> src(n);
+  for (int i = 0; i < n; ++i) {
+    ws[i] = lo.region_of(base, i);
+    src[i] = WgradSrc{dy[i], ws[i].dZ, ws[i].A, ws[i].Eraw, ws[i].Eact};
+  }
+  // the shading MLPs' shapes: the ring backward (nrt_train_ring.h), its job table in the
+  // weight-gradient table region; the saved path has no other kernel
+  const bool ring = saved || (!latent && ring_backward_ok(mlps, n) &&
+                              ring_backward_table_bytes(n) <= (size_t)n * kWgradTableBytes);
+  {
+    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M * n * (saved ? 0.5 : 1.0));
+    int rc = NRT_OK;
+    if (ring) {
+      std::vector<float*> A(n), dZ(n), Er(n), Ea(n), Ac(n, nullptr);
+      std::vector<const float*> Sr(n, nullptr), Sa(n, nullptr);
+      for (int i = 0; i < n; ++i) {
+        A[i] = ws[i].A; dZ[i] = ws[i].dZ; Er[i] = ws[i].Eraw; Ea[i] = ws[i].Eact;
+        if (!saved) continue;
+        const SavedActs sa = saved_split(d, Ms, saved[i]);
+        A[i] = sa.A; Sr[i] = sa.Eraw; Sa[i] = sa.Eact;
+        if (rows) {
+          // compacted rows: the backward copies the saved rows it reads into the workspace (the
+          // weight gradients' operands, row-aligned with dZ)
+          Ac[i] = ws[i].A;
+        } else {  // Ms == M: the saved activations themselves
+          Er[i] = Ea[i] = nullptr;
+          src[i].A = sa.A; src[i].Eraw = sa.Eraw; src[i].Eact = sa.Eact;
+        }
+      }
+      rc = ring_backward(mlps, n, x, M, dy, dx, A.data(), dZ.data(), Er.data(), Ea.data(), table,
+                         st, rows, saved ? Ms : -1, Ac.data(), Sr.data(), Sa.data());
+    } else {
+      std::vector<BwdJob> jobs(n);
+      for (int i = 0; i < n; ++i) {
+        const TrainWs& w = ws[i];
+        jobs[i] = BwdJob{mlps[i]->dev, dy[i], dx ? dx[i] : nullptr, w.Z, w.A, w.Eraw, w.Eact,
+                         w.dZ, w.Et, w.Gt};
+      }
+      rc = launch_slab(d, jobs.data(), n, (BwdJob*)(base + lo.jobs), x, latent, dlatent, M, st);
+    }
+    if (rc) return rc;
+  }
+  if (!dweights && !dbiases) return NRT_OK;
+  // every weight and bias gradient in one batched split-K launch (+ its slice reduction)
+  WgradBatch batch;
+  batch.max_jobs = n * kMaxWgradJobs;
+  batch.slices = lo.slices;
+  for (int i = 0; i < n; ++i) fill_wgrad(batch, d, false, M, &src[i], of(dweights, i), of(dbiases, i));
+  return batch.run(table, (float*)(base + lo.part), lo.part_floats, st);
 }
 }  // namespace
 
@@ -1505,13 +1652,7 @@ using namespace nrt;
 extern "C" {
 
 size_t nrt_mlp_backward_workspace_bytes(const nrt_mlp* m, int64_t M) {
-  if (!m) return 0;
-  M = std::max<int64_t>(M, 1);
-  const MlpDev& d = m->host_dev;
-  const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
-  const size_t enc = (size_t)M * d.dp * 4;
-  return 3 * a256(lay) + 2 * a256(enc) + 2 * a256(enc_tile_bytes(d, M)) +
-         a256(kWgradTableBytes) + a256(batch_part_floats(d, M, false) * 4);
+  return nrt_mlp_backward_multi_workspace_bytes(&m, 1, M);
 }
 
 int nrt_mlp_backward(const nrt_mlp* m, const float* x, const float* latent, int64_t M,
@@ -1524,84 +1665,13 @@ int nrt_mlp_backward(const nrt_mlp* m, const float* x, const float* latent, int6
   const MlpDev& d = m->host_dev;
   if (d.latent > 0 && !latent) { set_error("nrt_mlp_backward: latent required"); return NRT_EINVAL; }
   if (M > INT32_MAX) { set_error("nrt_mlp_backward: at most 2^31-1 rows per call"); return NRT_EINVAL; }
-  hipStream_t st = (hipStream_t)stream;
-  const int L = d.n_hidden, H = d.hidden;
-  if (M == 0) {  // zero gradients
-    for (int l = 0; l < L + 2; ++l) {
-      const int R = l == L + 1 ? d.out : H;
-      const int C = m->host_w[l].size() / (size_t)R;
-      if (dweights && dweights[l]) NRT_HIP(hipMemsetAsync(dweights[l], 0, (size_t)R * C * 4, st));
-      if (dbiases && dbiases[l]) NRT_HIP(hipMemsetAsync(dbiases[l], 0, (size_t)R * 4, st));
-    }
-    return NRT_OK;
-  }
-  TrainWs w = carve(m, M, workspace);
-  bool tile = false;
-  const bool cs = option(OPT_BWD_COLSPLIT) != 0;
-  const LdsPlan lp = cs ? backward_plan_cs(d, tile) : backward_plan(d, tile);
-  const int waves = ceil_div64(M, 32);
-  dim3 grid(ceil_div64(waves, lp.waves)), block(64 * lp.waves);
-  int rc = NRT_OK;
-  // the shading MLPs' shapes: the ring backward (nrt_train_ring.h), its job table in the
-  // workspace's weight-gradient table region (the weight gradients copy theirs after it ran)
-  if (!latent && ring_backward_ok(&m, 1) && ring_backward_table_bytes(1) <= kWgradTableBytes) {
-    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M);
-    if ((rc = ring_backward(&m, 1, x, M, &dy, &dx, &w.A, &w.dZ, &w.Eraw, &w.Eact, w.table, st)))
-      return rc;
-  } else {
-    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M);
-    NRT_NB_SWITCH(d.nb, {
-      if (cs) {
-        const dim3 gcs(waves), bcs(64 * NRT_CW(NB));
-        if (tile) {
-          if (!(rc = set_lds(k_mlp_backward32_cs<NB, true>, lp.bytes)))
-            k_mlp_backward32_cs<NB, true><<<gcs, bcs, lp.bytes, st>>>(
-                m->dev, x, latent, M, dy, dx, dlatent, w.Z, w.A, w.Eraw, w.Eact, w.dZ, w.Et, w.Gt, lp.RS);
-        } else {
-          if (!(rc = set_lds(k_mlp_backward32_cs<NB, false>, lp.bytes)))
-            k_mlp_backward32_cs<NB, false><<<gcs, bcs, lp.bytes, st>>>(
-                m->dev, x, latent, M, dy, dx, dlatent, w.Z, w.A, w.Eraw, w.Eact, w.dZ, w.Et, w.Gt, lp.RS);
-        }
-      } else if (tile) {
-        if (!(rc = set_lds(k_mlp_backward32<NB, true>, lp.bytes)))
-          k_mlp_backward32<NB, true><<<grid, block, lp.bytes, st>>>(
-              m->dev, x, latent, M, dy, dx, dlatent, w.Z, w.A, w.Eraw, w.Eact, w.dZ, w.Et, w.Gt,
-              lp.RS, lp.per_wave);
-      } else {
-        if (!(rc = set_lds(k_mlp_backward32<NB, false>, lp.bytes)))
-          k_mlp_backward32<NB, false><<<grid, block, lp.bytes, st>>>(
-              m->dev, x, latent, M, dy, dx, dlatent, w.Z, w.A, w.Eraw, w.Eact, w.dZ, w.Et, w.Gt,
-              lp.RS, lp.per_wave);
-      }
-    });
-    if (rc) return rc;
-    if ((rc = check_launch("k_mlp_backward32"))) return rc;
-  }
-  if (!dweights && !dbiases) return NRT_OK;
-  // every weight and bias gradient in one batched split-K launch (+ its slice reduction)
-  const size_t lay = (size_t)M * H;
-  WgradBatch batch;
-  const size_t cap = batch_part_floats(d, M, false, &batch.slices);
-  backward_jobs(d, false, [&](int l, int R, int kind, int C, int ldw, int c0) {
-    const float* dZ = l == L + 1 ? dy : w.dZ + (size_t)l * lay;
-    if (kind == 3) {
-      if (dbiases && dbiases[l]) batch.bias(dZ, R, M, dbiases[l]);
-      return;
-    }
-    if (!dweights || !dweights[l]) return;
-    const float* In = kind == 0 ? w.Eraw : kind == 1 ? w.A + (size_t)(l - 1) * lay : w.Eact;
-    batch.weight(dZ, R, In, C, M, dweights[l], ldw, c0);
-  });
-  return batch.run(w.table, w.part, cap, st);
+  return backward_core(&m, 1, x, latent, M, nullptr, nullptr, -1, &dy, &dx, dlatent, dweights,
+                       dbiases, workspace, (hipStream_t)stream);
 }
 
 size_t nrt_mlp_backward_multi_workspace_bytes(const nrt_mlp* const* mlps, int n, int64_t M) {
   if (!mlps || n <= 0 || !mlps[0]) return 0;
-  M = std::max<int64_t>(M, 1);
-  const MlpDev& d = mlps[0]->host_dev;
-  const size_t part = multi_part_floats(d, n, M);
-  return (size_t)n * region_bytes(d, M) + a256((size_t)n * sizeof(BwdJob)) +
-         a256((size_t)n * kWgradTableBytes) + a256(part * 4);
+  return TrainLayout(mlps[0]->host_dev, n, std::max<int64_t>(M, 1)).bytes;
 }
 
 int nrt_mlp_backward_multi(const nrt_mlp* const* mlps, int n, const float* x, int64_t M,
@@ -1620,84 +1690,8 @@ int nrt_mlp_backward_multi(const nrt_mlp* const* mlps, int n, const float* x, in
   const MlpDev& d = mlps[0]->host_dev;
   if (d.latent > 0) { set_error("nrt_mlp_backward_multi: latent MLPs are not supported"); return NRT_EINVAL; }
   if (M > INT32_MAX) { set_error("nrt_mlp_backward_multi: at most 2^31-1 rows per call"); return NRT_EINVAL; }
-  const int L = d.n_hidden, H = d.hidden, NL = L + 2;
-  if (M == 0) {
-    for (int i = 0; i < n; ++i)
-      if (int rc = nrt_mlp_backward(mlps[i], x, nullptr, 0, dy[i], nullptr, nullptr,
-                                    dweights ? dweights + (size_t)i * NL : nullptr,
-                                    dbiases ? dbiases + (size_t)i * NL : nullptr, workspace, stream))
-        return rc;
-    return NRT_OK;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)workspace;
-  std::vector<TrainWs> ws(n);
-  std::vector<BwdJob> jobs(n);
-  for (int i = 0; i < n; ++i) {
-    ws[i] = carve(mlps[i], M, p);  // its first seven arrays; table / part are not used
-    p += region_bytes(d, M);
-    jobs[i] = BwdJob{mlps[i]->dev, dy[i], dx ? dx[i] : nullptr, ws[i].Z, ws[i].A, ws[i].Eraw,
-                     ws[i].Eact, ws[i].dZ, ws[i].Et, ws[i].Gt};
-  }
-  BwdJob* tj = (BwdJob*)p;
-  p += a256((size_t)n * sizeof(BwdJob));
-  void* table = p;
-  p += a256((size_t)n * kWgradTableBytes);
-  float* part = (float*)p;
-  NRT_HIP(hipMemcpyAsync(tj, jobs.data(), (size_t)n * sizeof(BwdJob), hipMemcpyHostToDevice, st));
-  bool tile = false;
-  const bool cs = option(OPT_BWD_COLSPLIT) != 0;
-  const LdsPlan lp = cs ? backward_plan_cs(d, tile) : backward_plan(d, tile);
-  const int waves = ceil_div64(M, 32);
-  dim3 grid(ceil_div64(waves, lp.waves), n), block(64 * lp.waves);
-  int rc = NRT_OK;
-  if (ring_backward_ok(mlps, n) && ring_backward_table_bytes(n) <= (size_t)n * kWgradTableBytes) {
-    // the ring backward (nrt_train_ring.h), blockIdx.y = MLP; its job table in the weight-gradient
-    // table region
-    std::vector<float*> A(n), dZ(n), Er(n), Ea(n);
-    for (int i = 0; i < n; ++i) { A[i] = ws[i].A; dZ[i] = ws[i].dZ; Er[i] = ws[i].Eraw; Ea[i] = ws[i].Eact; }
-    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M * n);
-    if ((rc = ring_backward(mlps, n, x, M, dy, dx, A.data(), dZ.data(), Er.data(), Ea.data(), table, st)))
-      return rc;
-  } else {
-    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M * n);
-    NRT_NB_SWITCH(d.nb, {
-      if (cs) {
-        const dim3 gcs(waves, n), bcs(64 * NRT_CW(NB));
-        if (tile) {
-          if (!(rc = set_lds(k_mlp_backward32_multi_cs<NB, true>, lp.bytes)))
-            k_mlp_backward32_multi_cs<NB, true><<<gcs, bcs, lp.bytes, st>>>(tj, x, M, lp.RS);
-        } else {
-          if (!(rc = set_lds(k_mlp_backward32_multi_cs<NB, false>, lp.bytes)))
-            k_mlp_backward32_multi_cs<NB, false><<<gcs, bcs, lp.bytes, st>>>(tj, x, M, lp.RS);
-        }
-      } else if (tile) {
-        if (!(rc = set_lds(k_mlp_backward32_multi<NB, true>, lp.bytes)))
-          k_mlp_backward32_multi<NB, true><<<grid, block, lp.bytes, st>>>(tj, x, M, lp.RS, lp.per_wave);
-      } else {
-        if (!(rc = set_lds(k_mlp_backward32_multi<NB, false>, lp.bytes)))
-          k_mlp_backward32_multi<NB, false><<<grid, block, lp.bytes, st>>>(tj, x, M, lp.RS, lp.per_wave);
-      }
-    });
-    if (rc) return rc;
-    if ((rc = check_launch("k_mlp_backward32_multi"))) return rc;
-  }
-  if (!dweights && !dbiases) return NRT_OK;
-  const size_t lay = (size_t)M * H;
-  WgradBatch batch;
-  const size_t cap = multi_part_floats(d, n, M, &batch.slices);
-  multi_jobs(d, n, M, batch, [&](int i, int l, int R, int kind, int C, int ldw, int c0) {
-    const TrainWs& w = ws[i];
-    const float* dZ = l == L + 1 ? dy[i] : w.dZ + (size_t)l * lay;
-    if (kind == 3) {
-      if (dbiases && dbiases[(size_t)i * NL + l]) batch.bias(dZ, R, M, dbiases[(size_t)i * NL + l]);
-      return;
-    }
-    if (!dweights || !dweights[(size_t)i * NL + l]) return;
-    const float* In = kind == 0 ? w.Eraw : kind == 1 ? w.A + (size_t)(l - 1) * lay : w.Eact;
-    batch.weight(dZ, R, In, C, M, dweights[(size_t)i * NL + l], ldw, c0);
-  });
-  return batch.run(table, part, cap, st);
+  return backward_core(mlps, n, x, nullptr, M, nullptr, nullptr, -1, dy, dx, nullptr, dweights,
+                       dbiases, workspace, (hipStream_t)stream);
 }
 
 int nrt_mlp_backward_saved(const nrt_mlp* const* mlps, int n, const float* x, int64_t M,
@@ -1715,85 +1709,19 @@ int nrt_mlp_backward_saved(const nrt_mlp* const* mlps, int n, const float* x, in
       return NRT_EINVAL;
     }
   }
-  const MlpDev& d = mlps[0]->host_dev;
   if (M > INT32_MAX || Ms > INT32_MAX) { set_error("nrt_mlp_backward_saved: at most 2^31-1 rows per call"); return NRT_EINVAL; }
   if (!ring_backward_ok(mlps, n)) {
     set_error("nrt_mlp_backward_saved: no ring backward for these MLPs (nrt_mlp_save_bytes is 0)");
     return NRT_EUNSUPPORTED;
   }
-  const int L = d.n_hidden, H = d.hidden, NL = L + 2;
-  if (M == 0)
-    return nrt_mlp_backward_multi(mlps, n, x, 0, dy, dx, dweights, dbiases, workspace, stream);
-  hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)workspace;  // nrt_mlp_backward_multi_workspace_bytes(mlps, n, M)
-  std::vector<TrainWs> ws(n);
-  std::vector<SavedActs> sa(n);
-  std::vector<float*> A(n), dZ(n), Ac(n), Er(n), Ea(n);
-  std::vector<const float*> Sr(n), Sa(n);
-  for (int i = 0; i < n; ++i) {
-    ws[i] = carve(mlps[i], M, p);
-    p += region_bytes(d, M);
-    sa[i] = saved_split(d, Ms, saved[i]);
-    A[i] = sa[i].A;
-    dZ[i] = ws[i].dZ;
-    // compacted rows: the backward copies the saved rows it reads into the workspace (the
-    // weight gradients' operands, row-aligned with dZ)
-    Ac[i] = ws[i].A; Er[i] = ws[i].Eraw; Ea[i] = ws[i].Eact;
-    Sr[i] = sa[i].Eraw; Sa[i] = sa[i].Eact;
-    if (!rows) { Ac[i] = nullptr; Er[i] = nullptr; Ea[i] = nullptr; }
-  }
-  p += a256((size_t)n * sizeof(BwdJob));
-  void* table = p;
-  p += a256((size_t)n * kWgradTableBytes);
-  float* part = (float*)p;
-  int rc = NRT_OK;
-  {
-    ProfScope prof("k_mlp_backward32", st, bwd_row_flop(d) * (double)M * n * 0.5);
-    if ((rc = ring_backward(mlps, n, x, M, dy, dx, A.data(), dZ.data(), Er.data(), Ea.data(), table, st,
-                            rows, Ms, Ac.data(), Sr.data(), Sa.data())))
-      return rc;
-  }
-  if (!dweights && !dbiases) return NRT_OK;
-  const size_t lay = (size_t)M * H;
-  WgradBatch batch;
-  const size_t cap = multi_part_floats(d, n, M, &batch.slices);
-  multi_jobs(d, n, M, batch, [&](int i, int l, int R, int kind, int C, int ldw, int c0) {
-    const float* dZl = l == L + 1 ? dy[i] : ws[i].dZ + (size_t)l * lay;
-    if (kind == 3) {
-      if (dbiases && dbiases[(size_t)i * NL + l]) batch.bias(dZl, R, M, dbiases[(size_t)i * NL + l]);
-      return;
-    }
-    if (!dweights || !dweights[(size_t)i * NL + l]) return;
-    // without compaction the saved activations themselves (Ms == M), else their compacted copy
-    const float* Ar = rows ? ws[i].A : sa[i].A;
-    const float* In = kind == 0 ? (rows ? ws[i].Eraw : sa[i].Eraw)
-                    : kind == 1 ? Ar + (size_t)(l - 1) * lay
-                                : (rows ? ws[i].Eact : sa[i].Eact);
-    batch.weight(dZl, R, In, C, M, dweights[(size_t)i * NL + l], ldw, c0);
-  });
-  return batch.run(table, part, cap, st);
-}
-
-static size_t gb_sizes(const MlpDev& d, int64_t M, size_t sz[9]) {
-  const size_t lay = (size_t)(d.n_hidden + 1) * (size_t)M * d.hidden * 4;
-  sz[0] = lay;          // Z
-  sz[1] = lay;          // Z tangent
-  sz[2] = 2 * lay;      // A stacked
-  sz[3] = 2 * lay;      // dZ stacked
-  sz[4] = (size_t)2 * M * d.dp * 4;   // E0
-  sz[5] = sz[4];                      // E1
-  sz[6] = (size_t)2 * M * d.out * 4;  // output seed
-  sz[7] = kWgradTableBytes;                          // weight-gradient job table
-  sz[8] = batch_part_floats(d, M, true) * 4;        // batched split-K partial products
-  size_t tot = 0;
-  for (int i = 0; i < 9; ++i) tot += a256(sz[i]);
-  return tot;
+  // workspace: nrt_mlp_backward_multi_workspace_bytes(mlps, n, M)
+  return backward_core(mlps, n, x, nullptr, M, rows, saved, Ms, dy, dx, nullptr, dweights, dbiases,
+                       workspace, (hipStream_t)stream);
 }
 
 size_t nrt_mlp_grad_backward_workspace_bytes(const nrt_mlp* m, int64_t M) {
   if (!m) return 0;
-  size_t sz[9];
-  return gb_sizes(m->host_dev, std::max<int64_t>(M, 1), sz);
+  return GradBwdLayout(m->host_dev, std::max<int64_t>(M, 1)).bytes;
 }
 
 int nrt_mlp_grad_backward(const nrt_mlp* m, const float* x, const float* latent, int64_t M,
@@ -1808,22 +1736,10 @@ int nrt_mlp_grad_backward(const nrt_mlp* m, const float* x, const float* latent,
   if (M > INT32_MAX / 2) { set_error("nrt_mlp_grad_backward: at most 2^30-1 rows per call"); return NRT_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   const int L = d.n_hidden, H = d.hidden;
-  auto zero_all = [&]() -> int {
-    for (int l = 0; l < L + 2; ++l) {
-      const int R = l == L + 1 ? d.out : H;
-      const int C = m->host_w[l].size() / (size_t)R;
-      if (dweights && dweights[l]) NRT_HIP(hipMemsetAsync(dweights[l], 0, (size_t)R * C * 4, st));
-      if (dbiases && dbiases[l]) NRT_HIP(hipMemsetAsync(dbiases[l], 0, (size_t)R * 4, st));
-    }
-    return NRT_OK;
-  };
-  if (M == 0) return zero_all();
+  if (M == 0) return zero_grads(m, dweights, dbiases, st);
   if (!dweights && !dbiases) return NRT_OK;
-  size_t sz[9];
-  gb_sizes(d, M, sz);
-  float* buf[9];
-  char* p = (char*)workspace;
-  for (int i = 0; i < 9; ++i) { buf[i] = (float*)p; p += a256(sz[i]); }
+  const GradBwdLayout lo(d, M);
+  auto at = [&](size_t off) { return (float*)((char*)workspace + off); };
   // slab row: primal activations | encoding | encoding tangent | tangent activations
   const int RS = (2 * std::max(H, 32) + 2 * std::max(d.ke, 16)) | 1;
   const int per_wave = 32 * RS;
@@ -1841,38 +1757,28 @@ int nrt_mlp_grad_backward(const nrt_mlp* m, const float* x, const float* latent,
         const size_t bcs = (size_t)per_wave * 4;
         if (!(rc = set_lds(k_mlp_grad_backward32_cs<NB>, bcs)))
           k_mlp_grad_backward32_cs<NB><<<dim3(nwaves), dim3(64 * NB), bcs, st>>>(
-              m->dev, x, latent, v, M, buf[0], buf[1], buf[2], buf[4], buf[5], buf[3], RS);
+              m->dev, x, latent, v, M, at(lo.Z), at(lo.T), at(lo.A), at(lo.E0), at(lo.E1), at(lo.dZ), RS);
       } else if (!(rc = set_lds(k_mlp_grad_backward32<NB>, bytes)))
-        k_mlp_grad_backward32<NB><<<grid, block, bytes, st>>>(m->dev, x, latent, v, M, buf[0], buf[1],
-                                                             buf[2], buf[4], buf[5], buf[3], RS,
-                                                             per_wave);
+        k_mlp_grad_backward32<NB><<<grid, block, bytes, st>>>(
+            m->dev, x, latent, v, M, at(lo.Z), at(lo.T), at(lo.A), at(lo.E0), at(lo.E1), at(lo.dZ), RS,
+            per_wave);
     });
     if (rc) return rc;
     if ((rc = check_launch("k_mlp_grad_backward32"))) return rc;
   }
-  const int64_t M2 = 2 * M;
-  float* seed = buf[6];
-  float* part = buf[7];
+  // the out layer's dZ: zeros over the primal rows, ones over the tangent rows
+  float* seed = at(lo.seed);
   NRT_HIP(hipMemsetAsync(seed, 0, (size_t)M * d.out * 4, st));
   k_fill<><<<dim3(std::min<int64_t>(ceil_div64(M * d.out, 256), 1024)), dim3(256), 0, st>>>(
       seed + (size_t)M * d.out, M * d.out, 1.f);
   if ((rc = check_launch("k_fill"))) return rc;
-  const size_t lay2 = (size_t)M2 * H;
   // the out layer's bias takes no gradient from J (its tangent rows carry no bias)
   if (dbiases && dbiases[L + 1]) NRT_HIP(hipMemsetAsync(dbiases[L + 1], 0, (size_t)d.out * 4, st));
+  const WgradSrc src{seed, at(lo.dZ), at(lo.A), at(lo.E0), at(lo.E1)};
   WgradBatch batch;
-  const size_t cap = batch_part_floats(d, M, true, &batch.slices);
-  backward_jobs(d, true, [&](int l, int R, int kind, int C, int ldw, int c0) {
-    const float* dZ = l == L + 1 ? seed : buf[3] + (size_t)l * lay2;
-    if (kind == 3) {  // bias: the primal rows only
-      if (dbiases && dbiases[l]) batch.bias(dZ, R, M, dbiases[l]);
-      return;
-    }
-    if (!dweights || !dweights[l]) return;
-    const float* In = kind == 0 ? buf[4] : kind == 1 ? buf[2] + (size_t)(l - 1) * lay2 : buf[5];
-    batch.weight(dZ, R, In, C, M2, dweights[l], ldw, c0);
-  });
-  return batch.run(part, buf[8], cap, st);
+  batch.slices = lo.slices;
+  fill_wgrad(batch, d, true, M, &src, dweights, dbiases);
+  return batch.run(at(lo.table), at(lo.part), lo.part_floats, st);
 }
 
 }  // extern "C"

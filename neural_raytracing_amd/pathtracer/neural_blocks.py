@@ -175,50 +175,63 @@ def _live_rows(dys, M):
     return None if idx.numel() > (1.0 - COMPACT_MIN_DEAD) * M else idx
 
 
-def mlp_first_order(mlp, handle, save, x, lat, dy, want_dx, want_dlat):
-    """One MLP backward on the packed weights of ``handle``: (dL/dx, dL/dlatent, [dW0, db0, dW1,
-    ...]) from nrt_mlp_backward_saved when the forward saved its activations (``save``, from
-    _forward_saving), else nrt_mlp_backward.  Shared by _MlpFn and the fused volume render."""
+def _first_order(mlps, handles, saves, x, lat, dys, want_dx, want_dlat):
+    """The first-order backward of same-shape MLPs on one input, on the packed weights of
+    ``handles``: (dL/dx summed over the MLPs, dL/dlatent, [dW0, db0, dW1, ...] of each MLP in
+    turn).  With the forward's saved activations (``saves``, from _forward_saving)
+    nrt_mlp_backward_saved, else the recomputing nrt_mlp_backward_multi; a latent MLP (one MLP a
+    call) takes nrt_mlp_backward."""
     import ctypes
     lib = _lib.load(require_device=True)
-    M = x.shape[0]
-    dy = dy.detach().float().contiguous()
-    lins = mlp._linears()
-    idx = _live_rows([dy], M)
-    if idx is not None:  # the rows with a gradient only (COMPACT_MIN_DEAD)
-        full_x, full_lat = x, lat
-        x, dy = x[idx].contiguous(), dy[idx].contiguous()
+    P = ctypes.c_void_p
+    n, M = len(mlps), x.shape[0]
+    dys = [dy.detach().float().contiguous() for dy in dys]
+    full_x, full_lat = x, lat
+    idx = _live_rows(dys, M)
+    if idx is not None:  # the rows where any of the MLPs has a gradient (COMPACT_MIN_DEAD)
+        x = x[idx].contiguous()
+        dys = [dy[idx].contiguous() for dy in dys]
         lat = None if lat is None else lat[idx].contiguous()
         M = x.shape[0]
-    dx = torch.empty_like(x) if want_dx else None
+    dx = torch.empty(n, M, x.shape[1], device=x.device) if want_dx else None
     dlat = torch.empty_like(lat) if (lat is not None and want_dlat) else None
-    zeros = M == 0
-    mk = torch.zeros_like if zeros else torch.empty_like
-    dws = [mk(lin.weight) if lin.weight.requires_grad else None for lin in lins]
-    dbs = [mk(lin.bias) if lin.bias.requires_grad else None for lin in lins]
-    wp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dws])
-    bp = (ctypes.c_void_p * len(lins))(*[0 if t is None else t.data_ptr() for t in dbs])
-    if not zeros and save is not None:  # the forward saved the activations
-        P = ctypes.c_void_p
-        ws = torch.empty(lib.nrt_mlp_backward_multi_workspace_bytes((P * 1)(handle.value), 1, M),
-                         dtype=torch.uint8, device=x.device)
-        rows = None if idx is None else idx.to(torch.int32)
-        _lib.call("nrt_mlp_backward_saved", (P * 1)(handle.value), 1, _lib.ptr(x), M,
-                  _lib.ptr(rows), (P * 1)(save[0].data_ptr()), full_x.shape[0] if idx is not None else M,
-                  (P * 1)(dy.data_ptr()), None if dx is None else (P * 1)(dx.data_ptr()),
-                  wp, bp, _lib.ptr(ws), _lib.stream())
-    elif not zeros:
-        ws = torch.empty(lib.nrt_mlp_backward_workspace_bytes(handle.value, M),
-                         dtype=torch.uint8, device=x.device)
-        _lib.call("nrt_mlp_backward", handle.value, _lib.ptr(x), _lib.ptr(lat), M,
-                  _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dlat), wp, bp, _lib.ptr(ws),
-                  _lib.stream())
+    mk = torch.zeros_like if M == 0 else torch.empty_like
+    grads = [mk(t) if t.requires_grad else None
+             for m in mlps for lin in m._linears() for t in (lin.weight, lin.bias)]
+    if M > 0:
+        def ptrs(ts):
+            return (P * len(ts))(*[0 if t is None else t.data_ptr() for t in ts])
+        hs = (P * n)(*[h.value for h in handles])
+        dyp, wp, bp = ptrs(dys), ptrs(grads[0::2]), ptrs(grads[1::2])
+        dxp = None if dx is None else ptrs(list(dx))
+        # (the single entry's workspace is the multi entry's with n == 1)
+        ws = torch.empty(lib.nrt_mlp_backward_multi_workspace_bytes(hs, n, M), dtype=torch.uint8,
+                         device=x.device)
+        if lat is not None:
+            _lib.call("nrt_mlp_backward", handles[0].value, _lib.ptr(x), _lib.ptr(lat), M,
+                      _lib.ptr(dys[0]), None if dx is None else _lib.ptr(dx[0]), _lib.ptr(dlat),
+                      wp, bp, _lib.ptr(ws), _lib.stream())
+        elif saves is not None:  # the forward saved the activations
+            rows = None if idx is None else idx.to(torch.int32)
+            _lib.call("nrt_mlp_backward_saved", hs, n, _lib.ptr(x), M, _lib.ptr(rows), ptrs(saves),
+                      full_x.shape[0], dyp, dxp, wp, bp, _lib.ptr(ws), _lib.stream())
+        else:
+            _lib.call("nrt_mlp_backward_multi", hs, n, _lib.ptr(x), M, dyp, dxp, wp, bp,
+                      _lib.ptr(ws), _lib.stream())
+    if dx is not None:  # (one MLP: no sum, which would turn a -0.0 into +0.0 and add a kernel)
+        dx = dx[0] if n == 1 else dx.sum(0)
     if idx is not None:  # scatter back: dL/dx = 0 on the rows without a gradient
         if dx is not None:
             dx = torch.zeros_like(full_x).index_copy_(0, idx, dx)
         if dlat is not None:
             dlat = torch.zeros_like(full_lat).index_copy_(0, idx, dlat)
-    return dx, dlat, [g for pair in zip(dws, dbs) for g in pair]
+    return dx, dlat, grads
+
+
+def mlp_first_order(mlp, handle, save, x, lat, dy, want_dx, want_dlat):
+    """_first_order for one MLP: (dL/dx, dL/dlatent, [dW0, db0, dW1, ...]).  Shared by _MlpFn and
+    the fused volume render."""
+    return _first_order([mlp], [handle], save, x, lat, [dy], want_dx, want_dlat)
 
 
 class _MlpFn(torch.autograd.Function):
@@ -365,7 +378,6 @@ class _MultiMlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mlps, x, *params):
-        import ctypes
         handles = [train_handle(m) for m in mlps]
         with torch.no_grad():
             ys, ctx.save = _forward_saving(handles, x.detach(), [m.out.out_features for m in mlps],
@@ -378,53 +390,14 @@ class _MultiMlpFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        import ctypes
         _check_versions(ctx)
         if torch.is_grad_enabled():
             raise _lib.NrtError("second derivatives through SkipConnMLP.forward are not on the HIP "
                                 "path")
         (x,) = ctx.saved_tensors
-        mlps, n, M = ctx.mlps, len(ctx.mlps), x.shape[0]
-        lib = _lib.load(require_device=True)
-        dys = [dy.float().contiguous() for dy in dys]
-        idx = _live_rows(dys, M)
-        if idx is not None:  # the rows where any of the MLPs has a gradient (COMPACT_MIN_DEAD)
-            full_x = x
-            x = x[idx].contiguous()
-            dys = [dy[idx].contiguous() for dy in dys]
-            M = x.shape[0]
-        zeros = M == 0
-        mk = torch.zeros_like if zeros else torch.empty_like
-        dx = torch.empty(n, M, x.shape[1], device=x.device) if ctx.needs_input_grad[1] else None
-        grads, wptr, bptr = [], [], []
-        for m in mlps:
-            for lin in m._linears():
-                dw = mk(lin.weight) if lin.weight.requires_grad else None
-                db = mk(lin.bias) if lin.bias.requires_grad else None
-                grads += [dw, db]
-                wptr.append(0 if dw is None else dw.data_ptr())
-                bptr.append(0 if db is None else db.data_ptr())
-        P = ctypes.c_void_p
-        hs = (P * n)(*[h.value for h in ctx.handles])
-        dyp = (P * n)(*[d.data_ptr() for d in dys])
-        dxp = None if dx is None else (P * n)(*[dx[i].data_ptr() for i in range(n)])
-        wp, bp = (P * len(wptr))(*wptr), (P * len(bptr))(*bptr)
-        if not zeros:
-            ws = torch.empty(lib.nrt_mlp_backward_multi_workspace_bytes(hs, n, M),
-                             dtype=torch.uint8, device=x.device)
-            if ctx.save is not None:  # the forward saved the activations
-                rows = None if idx is None else idx.to(torch.int32)
-                Ms = full_x.shape[0] if idx is not None else M
-                _lib.call("nrt_mlp_backward_saved", hs, n, _lib.ptr(x), M, _lib.ptr(rows),
-                          (P * n)(*[b.data_ptr() for b in ctx.save]), Ms, dyp, dxp, wp, bp,
-                          _lib.ptr(ws), _lib.stream())
-            else:
-                _lib.call("nrt_mlp_backward_multi", hs, n, _lib.ptr(x), M, dyp, dxp, wp, bp,
-                          _lib.ptr(ws), _lib.stream())
-        dxs = None if dx is None else (dx.sum(0) if not zeros else torch.zeros_like(x))
-        if idx is not None and dxs is not None:
-            dxs = torch.zeros_like(full_x).index_copy_(0, idx, dxs)
-        return (None, dxs, *grads)
+        dx, _, grads = _first_order(ctx.mlps, ctx.handles, ctx.save, x, None, dys,
+                                    ctx.needs_input_grad[1], False)
+        return (None, dx, *grads)
 
 
 def input_gradient(mlp, x):

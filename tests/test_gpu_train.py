@@ -94,9 +94,10 @@ def test_mlp_backward_matches_autograd(name, M):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_weight_gradients_batch_kernel_matches_autograd(name):
-    """The weight gradients on k_wgrad_batch (option wgrad_tile 0: 64 x 64 tiles fed by direct
-    loads, separate bias column sums) as well as on the default k_wgrad_tile (128 x 128 tiles
-    staged through LDS, biases summed on the first weight tiles): both at the float64 bar, and
+    """The weight gradients on the default k_wgrad_batch (option wgrad_tile 0: 64 x 64 tiles fed
+    by direct loads, separate bias column sums) as well as on k_wgrad_tile (option wgrad_tile 1:
+    128 x 128 tiles staged through LDS, biases summed on the first weight tiles): both at the
+    float64 bar, and
     within FP32 summation-order noise of each other."""
     from neural_raytracing_amd import _lib, set_precision
     kw = SHAPES[name]
