@@ -45,7 +45,8 @@ def softplus(x):
     return F.softplus(x)
 
 
-ACTIVATIONS = {"leaky_relu": leaky_relu, "softplus": softplus, "sigmoid": torch.sigmoid}
+ACTIVATIONS = {"leaky_relu": leaky_relu, "softplus": softplus, "sigmoid": torch.sigmoid,
+               "relu": torch.relu}
 
 
 class SkipMLP(nn.Module):

@@ -191,11 +191,11 @@ def test_three_mlps_stay_inside_the_workspace(ring):
 SDF_SHAPE = dict(num_layers=8, hidden_size=64, in_size=3, out=1, freqs=16)
 
 
-def _grad_backward(L, mlp, x, v, dws, dbs):
+def _grad_backward(L, mlp, x, v, dws, dbs, lat=None):
     h, M = _handle(mlp), x.shape[0]
     g = _Guarded(L.load(True).nrt_mlp_grad_backward_workspace_bytes(h.value, M))
-    L.call("nrt_mlp_grad_backward", h.value, L.ptr(x), None, M, L.ptr(v), _ptrs(dws), _ptrs(dbs),
-           None if M == 0 else L.ptr(g.ws), L.stream())
+    L.call("nrt_mlp_grad_backward", h.value, L.ptr(x), L.ptr(lat), M, L.ptr(v), _ptrs(dws),
+           _ptrs(dbs), None if M == 0 else L.ptr(g.ws), L.stream())
     g.check("nrt_mlp_grad_backward")
 
 
