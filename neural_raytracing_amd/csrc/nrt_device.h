@@ -1681,11 +1681,16 @@ __device__ __forceinline__ void seg2(const float4* A, const float (&B)[NBV], f4v
   seg2<NQ, P0, BO>(A, B, a0, a1, [](int) {});
 }
 
+// encoding k-steps (4 slots each) that hold at least one of the MLP's dp = 2 F + 3 input slots
+__device__ __forceinline__ int live_ksteps(int freqs) { return (2 * freqs + 3 + 3) >> 2; }
+
 // seg2 for a four-sub-block chunk: NQ quads at ring positions P0 + 4u + b, four chains a[b];
-// each quad's four LDS reads issued one quad ahead of its MFMAs, side(u) before them
+// each quad's four LDS reads issued one quad ahead of its MFMAs, side(u) before them.  Only the
+// first nl (1..4, wave-uniform) k-steps of the last quad are issued: an encoding part passes its
+// live count (live_ksteps), a hidden part 4.
 template <int NQ, int P0, int BO, int NBV, class Side>
 __device__ __forceinline__ void seg4(const float4* A, const float (&B)[NBV], f4v (&a)[kSub],
-                                     Side&& side) {
+                                     Side&& side, int nl = 4) {
   float4 w[kSub];
 #pragma unroll
   for (int b = 0; b < kSub; ++b) w[b] = A[(P0 + b) * 64];
@@ -1695,14 +1700,22 @@ __device__ __forceinline__ void seg4(const float4* A, const float (&B)[NBV], f4v
     float4 n[kSub];
 #pragma unroll
     for (int b = 0; b < kSub; ++b) n[b] = (u + 1 < NQ) ? A[(P0 + kSub * (u + 1) + b) * 64] : w[b];
+    const bool full = u + 1 < NQ;  // every quad but the last has four live k-steps
 #pragma unroll
     for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].x, B[BO + 4 * u], a[b]);
+    // (three flat tests, not nested ones: nested, k_march32<64, 20, 8, softplus> spills 5 VGPRs)
+    if (full || nl > 1) {
 #pragma unroll
-    for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].y, B[BO + 4 * u + 1], a[b]);
+      for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].y, B[BO + 4 * u + 1], a[b]);
+    }
+    if (full || nl > 2) {
 #pragma unroll
-    for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].z, B[BO + 4 * u + 2], a[b]);
+      for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].z, B[BO + 4 * u + 2], a[b]);
+    }
+    if (full || nl > 3) {
 #pragma unroll
-    for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].w, B[BO + 4 * u + 3], a[b]);
+      for (int b = 0; b < kSub; ++b) a[b] = mfma4(w[b].w, B[BO + 4 * u + 3], a[b]);
+    }
 #pragma unroll
     for (int b = 0; b < kSub; ++b) w[b] = n[b];
   }
@@ -1734,11 +1747,20 @@ __device__ __forceinline__ float eval(Engine<KH, KE, WV>& E, const MlpDev& m, fl
   const int F = m.freqs, L = m.n_hidden, SK = m.skip;
   // encoding: k-step e of lane group g is slot 4 e + g: sin / cos of projection (4e + g) / 2
   // (utils.py:37-40, same fma order and accurate sincosf as the FP32 slab path), then x, zeros
+  // The MLP reads dp = 2F + 3 slots and the packer pads them to ke = 4 KE, a multiple of 16
+  // (nrt_pack.hip), so the padding lies in the last quad only: k-steps KE - 4 + nl .. KE - 1 hold
+  // zero weights.  acc + 0 * x is acc, so neither their inputs nor their MFMAs are needed (seg4).
+  const int nl = live_ksteps(F) - (KE - 4);  // live k-steps of the last encoding quad, 1..4
   float eraw[KE], eact[KE];
 #pragma unroll
   for (int e = 0; e < KE; ++e) {
     const int slot = 4 * e + g;
     float v = 0.f, tv = 0.f;  // value and (TAN) d/dx_{comp-1}
+    if (e > KE - 4 && e - (KE - 4) >= nl) {  // a padding k-step (wave-uniform): never read
+      eraw[e] = 0.f;
+      eact[e] = 0.f;
+      continue;
+    }
     if (slot < 2 * F) {
       const float4 b = E.lbasis[slot >> 1];
       float pr = x0 * b.x;
@@ -1818,7 +1840,7 @@ __device__ __forceinline__ float eval(Engine<KH, KE, WV>& E, const MlpDev& m, fl
 #pragma unroll
     for (int b = 0; b < kSub; ++b) a[b] = bias(0, kSub * ib + b);
     if (ib > 0) retire(ib - 1);
-    seg4<QE, 0, 0>(A, eraw, a, [](int) {});
+    seg4<QE, 0, 0>(A, eraw, a, [](int) {}, nl);
 #pragma unroll
     for (int b = 0; b < kSub; ++b) pend[b] = a[b];
     E.end();
@@ -1845,7 +1867,7 @@ __device__ __forceinline__ float eval(Engine<KH, KE, WV>& E, const MlpDev& m, fl
       E.end();
       if (skip) {  // the encoding part: a chunk of its own
         const float4* B = E.begin(CE, after, false);
-        seg4<QE, 0, 0>(B, eact, a, [](int) {});
+        seg4<QE, 0, 0>(B, eact, a, [](int) {}, nl);
         E.end();
       }
 #pragma unroll
