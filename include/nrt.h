@@ -561,7 +561,8 @@ int nrt_render_tile(const nrt_camera* host_cams, int32_t N, int32_t x0, int32_t 
  * rgb_s = sigmoid(MLP_8x64([latent, d, light])), composited with the reference's weights
  * (alpha = 1 - exp(-relu(alpha_raw) t), rolled cumprod with the last entry 1).
  * light[light_dim] (device) is the point light's location (envmap=False, light_dim 3) or
- * its envmap encoding from nrt_light_envmap (envmap=True, light_dim 3 bins^2).
+ * its envmap encoding from nrt_light_envmap (envmap=True, light_dim 3 bins^2); one light for
+ * every ray here, one row per camera in nrt_nerfle_forward_lights below.
  * first: 3 -> 65, second: (67 + light_dim) -> 3.  ts[S] device; rgb [P,3].  FP16 with the
  * default shapes runs the fused k_nerfle16 kernel -- for the envmap too: the envmap is one
  * constant per call, so its share of the colour MLP's input (W[:, env] env in the init and skip
@@ -579,6 +580,20 @@ size_t nrt_nerfle_workspace_bytes_for(const nrt_mlp* first, const nrt_mlp* secon
 int nrt_nerfle_forward(const nrt_mlp* first, const nrt_mlp* second, const float* rays, int64_t P,
                        const float* ts, int32_t S, const float* light, int32_t light_dim,
                        float* rgb, void* workspace, int precision, void* stream);
+/* One light per camera (nerf.py:193-197 broadcasts the light's rows over the camera axis of
+ * [N, W, H, B] rays): light [rows, light_dim] (device), ray p under row p / rays_per_light,
+ * P == rows * rays_per_light; rows == 1 is nrt_nerfle_forward (any P, the same bits).  Only the
+ * encoding differs per row.  The unfused path reads the ray's row when it assembles the colour
+ * MLP's input.  k_nerfle16 looks the row up per lane from the sample's ray (a 32-sample tile may
+ * straddle two cameras); the point light reads its location from the row table, the envmap fold
+ * becomes a one-hot: row r's fold sits in kernel input column 67 + r, up to 13 rows per program
+ * in the light k-step's free elements, more rows render in groups of 13 cameras with one folded
+ * program each.  The programs are rebuilt when any row changes (one 4 rows light_dim-byte
+ * read-back and one stream synchronisation per call).  Same workspace. */
+int nrt_nerfle_forward_lights(const nrt_mlp* first, const nrt_mlp* second, const float* rays,
+                              int64_t P, const float* ts, int32_t S, const float* light,
+                              int32_t light_dim, int64_t rows, int64_t rays_per_light, float* rgb,
+                              void* workspace, int precision, void* stream);
 
 /* PlainNeRF (shapes/nerf.py:9-74; replaces PlainNeRF.forward, nerf.py:46-74): per ray and depth
  * ts[s] (the caller's linspace(0.4, 2 + random()*0.1, S)),
@@ -601,6 +616,13 @@ int nrt_plain_nerf_forward(const nrt_mlp* first, const nrt_mlp* second, const fl
  * elev_azim_to_dir (utils.py:478-486) of meshgrid(linspace(0, 180, bins), linspace(0, 45, bins))
  * -> out[bins^2 * 3] (device).  Point lights only (NRT_EUNSUPPORTED otherwise). */
 int nrt_light_envmap(const nrt_light* light, int32_t bins, float* out, void* stream);
+/* The same encoding for every row of loc [rows, 3] (device; one light per camera, rows <= 65535)
+ * -> out [rows, bins^2 * 3] (device), without a light handle: intensity[3] (host), the falloff
+ * coefficients and the scale are PointLights' own and are shared by the rows.  Row r equals
+ * nrt_light_envmap of a point light at loc[r] bit for bit. */
+int nrt_light_envmap_rows(const float* loc, int64_t rows, const float* intensity, float constant,
+                          float linear, float square, float scale, int32_t bins, float* out,
+                          void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Volume-rendering training path of PlainNeRF and NeRFLE (torch autograd
@@ -630,8 +652,10 @@ int nrt_nerf_points(int32_t model, const float* rays, int64_t P, const float* ts
                     float* lat1, void* stream);
 /* The second MLP's inputs from first_out, each first_out row read once (nerf.py:57-63,
  * :181-202), and the compact alpha_raw [S, P] = first_out[:, 0] (+ noise [S, P] for
- * NRT_NERF_PLAIN, nerf.py:65-67; NULL: none).  extra: NERFLE's light encoding [extra_dim] or
- * PLAIN's latent [rows, extra_dim].  NERFLE ignores I, rays_per_latent, noise and lat2. */
+ * NRT_NERF_PLAIN, nerf.py:65-67; NULL: none).  extra: NERFLE's light encoding or PLAIN's latent,
+ * [rows, extra_dim]: ray p reads row p / rays_per_latent (for NERFLE the rays per light row,
+ * one light per camera; <= 0 or >= P: the one row every ray shares; else P a multiple of it).
+ * NERFLE ignores I, noise and lat2. */
 int nrt_nerf_assemble(int32_t model, const float* first_out, const float* rays, int64_t P,
                       int32_t S, const float* extra, int32_t extra_dim, int32_t I,
                       int64_t rays_per_latent, const float* noise, float* x2, float* lat2,
@@ -657,8 +681,10 @@ int nrt_nerf_composite_backward(int32_t model, const float* alpha_raw, const flo
                                 float* d_alpha_raw, float* d_rgb_raw, void* workspace,
                                 void* stream);
 /* The gradients of the inputs every sample shares, summed in two stages in a fixed order:
- *   NERFLE  out [dim] = sum_i d_second[i, 67:]  (d_second = the second MLP's dx [n, 67 + dim]:
- *           the expanded light encoding, nerf.py:193-197; d_first unused)
+ *   NERFLE  out [P / rays_per_latent, dim] = per light row, the sum over its rays' samples of
+ *           d_second[i, 67:]  (d_second = the second MLP's dx [n, 67 + dim]: the expanded light
+ *           encoding, nerf.py:193-197; d_first unused); rays_per_latent <= 0 or >= P: one row,
+ *           out [dim]
  *   PLAIN   out [P / rays_per_latent, dim] = per latent row, the sum over its rays' samples of
  *           d_first[i, :] + d_second[i, I:]  (the MLPs' dlatent [n, dim], [n, I + dim]: the
  *           expanded latent, nerf.py:52, :63); P a multiple of rays_per_latent. */

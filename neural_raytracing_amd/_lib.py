@@ -137,7 +137,10 @@ _SIGNATURES = {
     "nrt_nerfle_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),
     "nrt_nerfle_workspace_bytes_for": (ctypes.c_size_t, [_P, _P, _I64, _I32, _I32, _I32]),
     "nrt_nerfle_forward": (_I32, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _P, _P, _I32, _P]),
+    "nrt_nerfle_forward_lights": (_I32, [_P, _P, _P, _I64, _P, _I32, _P, _I32, _I64, _I64, _P, _P,
+                                         _I32, _P]),
     "nrt_light_envmap": (_I32, [_P, _I32, _P, _P]),
+    "nrt_light_envmap_rows": (_I32, [_P, _I64, _P, _F, _F, _F, _F, _I32, _P, _P]),
     "nrt_plain_nerf_workspace_bytes": (ctypes.c_size_t, [_P, _P, _I64, _I32]),
     "nrt_plain_nerf_forward": (_I32, [_P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _I32, _P]),
     "nrt_nerf_volume_workspace_bytes": (ctypes.c_size_t, [_I64, _I32, _I32]),

@@ -23,11 +23,13 @@ __global__ void k_nerf_points(const float* __restrict__ rays, int64_t P, const f
 }
 
 // second MLP input [latent (64) | r_d (3) | light encoding (LK)]   (nerf.py:182-203): the point
-// light's location (LK = 3) or its envmap over bins^2 directions (LK = 3 bins^2)
+// light's location (LK = 3) or its envmap over bins^2 directions (LK = 3 bins^2).  light is
+// [rows, LK]: ray p reads row p / rpl (the reference's broadcast over the camera axis,
+// nerf.py:193-197); rpl = 0: one row for every ray
 template <int = 0>
 __global__ void k_nerf_second_in(const float* __restrict__ first_out, const float* __restrict__ rays,
                                  int64_t P, int S, const float* __restrict__ light, int LK,
-                                 float* __restrict__ x2) {
+                                 int64_t rpl, float* __restrict__ x2) {
   const int64_t n = (int64_t)S * P;
   const int in2 = 67 + LK;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -37,7 +39,8 @@ __global__ void k_nerf_second_in(const float* __restrict__ first_out, const floa
     float* o = x2 + i * in2;
     for (int k = 0; k < 64; ++k) o[k] = f[1 + k];
     o[64] = rays[p * 6 + 3]; o[65] = rays[p * 6 + 4]; o[66] = rays[p * 6 + 5];
-    for (int k = 0; k < LK; ++k) o[67 + k] = light[k];
+    const float* lr = rpl > 0 ? light + (p / rpl) * LK : light;
+    for (int k = 0; k < LK; ++k) o[67 + k] = lr[k];
   }
 }
 
@@ -50,19 +53,34 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
 
 // PointLights.envmap(elev_azim_to_dir(meshgrid(linspace(0, 180, bins), linspace(0, 45, bins))))
 // (nerf.py:183-191, utils.py:478-486, lights.py:81-88); the degrees go in as radians, as there.
-template <int = 0>
-__global__ void k_light_envmap(const LightDev* __restrict__ lp, int bins, float* __restrict__ out) {
-  const LightDev& lt = *lp;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= bins * bins) return;
+__device__ __forceinline__ void light_envmap_at(const LightDev& lt, const float* loc, int bins,
+                                                int i, float* __restrict__ out) {
   const float limit = 3.14159265358979f - 1e-7f;
   const float elev = fminf(fmaxf(linspace_at(0.f, 180.f, bins, i / bins), -limit), limit);
   const float azim = fminf(fmaxf(linspace_at(0.f, 45.f, bins, i % bins), -limit), limit);
   const float dx = sinf(azim) * cosf(elev), dy = cosf(azim) * cosf(elev), dz = sinf(elev);
-  const float vx = dx - lt.loc[0], vy = dy - lt.loc[1], vz = dz - lt.loc[2];
+  const float vx = dx - loc[0], vy = dy - loc[1], vz = dz - loc[2];
   const float dist = sqrtf(vx * vx + vy * vy + vz * vz);
   const float fall = fmaxf((lt.c + lt.l * dist) + lt.q * (dist * dist), 1e-6f);
   for (int k = 0; k < 3; ++k) out[i * 3 + k] = lt.scaled_dir[k] / fall;
+}
+
+template <int = 0>
+__global__ void k_light_envmap(const LightDev* __restrict__ lp, int bins, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bins * bins) return;
+  light_envmap_at(*lp, lp->loc, bins, i, out);
+}
+
+// the same envmap for every row of loc [rows, 3] (one light per camera): out [rows, 3 bins^2];
+// lt holds the spectrum and falloff the rows share (its own location is unused)
+template <int = 0>
+__global__ void k_light_envmap_rows(const LightDev lt, const float* __restrict__ loc, int bins,
+                                    float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bins * bins) return;
+  const int64_t r = blockIdx.y;
+  light_envmap_at(lt, loc + r * 3, bins, i, out + r * 3 * bins * bins);
 }
 
 // nerf.py:203-214: rgb = sigmoid(second), sigma = relu(alpha_raw), a_s = 1 - exp(-sigma t_s)
@@ -428,11 +446,17 @@ __device__ __forceinline__ void split_h8(const float (&v)[8], h8& hi, h8& lo) {
   lo = __builtin_bit_cast(h8, l);
 }
 
-template <int WV, int TT>
+// ROWS false: one light for every ray, light[0..2] read once per kernel (the point light's
+// location, or the envmap fold's (1, 0, 0)).  ROWS true: one light row per rays_per_light rays,
+// looked up per lane from the sample's ray (a 32-sample tile may straddle two rays, and so two
+// cameras, when S is no multiple of 32): the point light reads its row of light [rows, 3]; the
+// envmap fold (onehot) sets a 1 in e8 slot 3 + row, the column that row's fold was built into
+// (build_nerf_program).
+template <int WV, int TT, bool ROWS>
 __global__ void __launch_bounds__(64 * WV, 1) k_nerfle16(
     const ProgDev prog, const float* __restrict__ rays, int64_t P, const float* __restrict__ ts,
-    int S, const float* __restrict__ light, float* __restrict__ alpha_raw,
-    float* __restrict__ rgb_raw) {
+    int S, const float* __restrict__ light, int64_t rays_per_light, int rows, int onehot,
+    float* __restrict__ alpha_raw, float* __restrict__ rgb_raw) {
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   const int64_t n = (int64_t)S * P;
   const int64_t per_block = 32 * TT * WV;
@@ -443,7 +467,8 @@ __global__ void __launch_bounds__(64 * WV, 1) k_nerfle16(
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const ProgMlp& m1 = prog.mlp[0];
   const ProgMlp& m2 = prog.mlp[1];
-  const float lx = light[0], ly = light[1], lz = light[2];
+  float lx = 0.f, ly = 0.f, lz = 0.f;
+  if constexpr (!ROWS) { lx = light[0]; ly = light[1]; lz = light[2]; }
   for (int64_t b0 = (int64_t)blockIdx.x * per_block; b0 < n; b0 += (int64_t)gridDim.x * per_block) {
     // tile q of this wave: samples b0 + 32 (TT wv + q) + [0, 32) (recomputed where needed: the
     // registers go to the MLPs)
@@ -478,9 +503,28 @@ __global__ void __launch_bounds__(64 * WV, 1) k_nerfle16(
         split_h8(v, e[q][2 + tt], lo[q][tt]);
       }
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (h == 0) {
-        const float* r = ray_of(q);
-        v[0] = r[3]; v[1] = r[4]; v[2] = r[5]; v[3] = lx; v[4] = ly; v[5] = lz;
+      if constexpr (!ROWS) {
+        if (h == 0) {
+          const float* r = ray_of(q);
+          v[0] = r[3]; v[1] = r[4]; v[2] = r[5]; v[3] = lx; v[4] = ly; v[5] = lz;
+        }
+      } else {
+        const int64_t g = sample(q);
+        const int64_t row64 = ((g < n ? g : n - 1) / S) / rays_per_light;
+        const int row = (int)(row64 < rows ? row64 : rows - 1);
+        if (h == 0) {
+          const float* r = ray_of(q);
+          v[0] = r[3]; v[1] = r[4]; v[2] = r[5];
+          if (!onehot) {
+            const float* lr = light + row * 3;
+            v[3] = lr[0]; v[4] = lr[1]; v[5] = lr[2];
+          }
+        }
+        if (onehot) {
+          const int slot = 3 + row - 8 * h;  // element 8 h + j of the k-step
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = j == slot ? 1.f : v[j];
+        }
       }
       split_h8(v, e[q][8], lo[q][6]);
     }
@@ -580,8 +624,13 @@ static bool nerf_fusable(const nrt_mlp* f, const nrt_mlp* s) {
 // the init and skip layers is W[:, env] . env and its row of the Fourier basis is env . B[env, :]
 // (both summed in double, rounded once to f32); columns 68-69 are zero.  x'.B' = x.B and
 // W' x' = W x up to the order of the sums: the FP16 kernel's products are unchanged in kind.
+// R > 1 envmap rows (one light per camera, env [R, LK]): the constant becomes a one-hot over
+// the rows.  Row r's fold sits in kernel input column 67 + r, element 3 + r of encoding k-step
+// e8, whose 16 elements hold r_d (3) and up to kNerfFoldRows = 13 rows with no extra k-step; a
+// lane's input is 1 in its row's column.  R = 1 builds the bytes the single fold always had.
+constexpr int kNerfFoldRows = 13;
 static int build_nerf_program(const nrt_mlp* f, const nrt_mlp* s, nrt_prog& out,
-                              const float* env = nullptr) {
+                              const float* env = nullptr, int R = 1) {
   out.ok = false;
   const MlpDev& a = f->host_dev;
   const MlpDev& b = s->host_dev;
@@ -610,11 +659,16 @@ static int build_nerf_program(const nrt_mlp* f, const nrt_mlp* s, nrt_prog& out,
     }
   }
   // element (h, j) of second-MLP encoding k-step e -> kernel input column (-1: none)
-  const int IN = 70, F = 16;
+  // IN: the kernel's input columns [latent 64 | r_d 3 | light 3, or the fold's 13 row columns]
+  const int IN = env ? 67 + kNerfFoldRows : 70, F = 16;
   const int INo = s->host_dev.in_size;  // the MLP's own input width (70, or 67 + 3 bins^2)
   const int LK = INo - 67;
   if (env == nullptr && INo != IN) {
     set_error("build_nerf_program: a NeRF+LE colour MLP needs its envmap");
+    return NRT_EINVAL;
+  }
+  if (R < 1 || R > kNerfFoldRows) {
+    set_error("build_nerf_program: 1..13 envmap rows per program");
     return NRT_EINVAL;
   }
   auto enc_col = [&](int e, int hf, int j) -> int {
@@ -627,14 +681,16 @@ static int build_nerf_program(const nrt_mlp* f, const nrt_mlp* s, nrt_prog& out,
       const int r = 32 * (t >> 1) + 16 * (t & 1) + 8 * (j >> 2) + 4 * hf + (j & 3);
       return (r >= 1 && r <= 64) ? r - 1 : -1;
     }
-    return (hf == 0 && j < 6) ? 64 + j : -1;
+    if (env == nullptr) return (hf == 0 && j < 6) ? 64 + j : -1;
+    return 8 * hf + j < 3 + R ? 64 + 8 * hf + j : -1;
   };
   // the second MLP's basis at kernel input column col (< IN), with the envmap fold
   auto basis_at = [&](int col, int q) -> float {
     if (env == nullptr || col < 67) return s->host_basis[(size_t)col * F + q];
-    if (col > 67) return 0.f;
+    if (col >= 67 + R) return 0.f;
+    const float* er = env + (size_t)(col - 67) * LK;
     double acc = 0.0;
-    for (int k = 0; k < LK; ++k) acc += (double)env[k] * s->host_basis[(size_t)(67 + k) * F + q];
+    for (int k = 0; k < LK; ++k) acc += (double)er[k] * s->host_basis[(size_t)(67 + k) * F + q];
     return (float)acc;
   };
   // weight of layer l at (row, kernel column col) of its [hidden? H | x (IN) | sin F | cos F]
@@ -647,9 +703,10 @@ static int build_nerf_program(const nrt_mlp* f, const nrt_mlp* s, nrt_prog& out,
       return W[(size_t)row * Co + base + oc];
     }
     if (ic >= IN) return W[(size_t)row * Co + base + INo + (ic - IN)];
-    if (ic > 67) return 0.f;
+    if (ic >= 67 + R) return 0.f;
+    const float* er = env + (size_t)(ic - 67) * LK;
     double acc = 0.0;
-    for (int k = 0; k < LK; ++k) acc += (double)W[(size_t)row * Co + base + 67 + k] * env[k];
+    for (int k = 0; k < LK; ++k) acc += (double)W[(size_t)row * Co + base + 67 + k] * er[k];
     return (float)acc;
   };
   // projection chunk: A[q][k] = basis[x index of k][q] split into hi and lo halves
@@ -786,54 +843,124 @@ int nrt_light_envmap(const nrt_light* l, int32_t bins, float* out, void* stream)
   return check_launch("k_light_envmap");
 }
 
-int nrt_nerfle_forward(const nrt_mlp* first, const nrt_mlp* second, const float* rays, int64_t P,
-                       const float* ts, int32_t S, const float* light, int32_t light_dim,
-                       float* rgb, void* workspace, int precision, void* stream) {
-  if (!first || !second || P < 0 || S < 1) { set_error("nrt_nerfle_forward: bad argument"); return NRT_EINVAL; }
-  if (P == 0) return NRT_OK;
-  if (!rays || !ts || !light || !rgb || !workspace) { set_error("nrt_nerfle_forward: null argument"); return NRT_EINVAL; }
-  if (first->desc.in_size != 3 || first->desc.out != 65 || light_dim < 3 ||
-      second->desc.in_size != 67 + light_dim || second->desc.out != 3) {
-    set_error("nrt_nerfle_forward: expects first 3 -> 65 and second (67 + light_dim) -> 3 "
-              "(nerf.py:162-172)");
+int nrt_light_envmap_rows(const float* loc, int64_t rows, const float* inten, float c, float lin,
+                          float q, float scale, int32_t bins, float* out, void* stream) {
+  if (rows < 0 || rows > 65535 || bins < 1 || !inten) {
+    set_error("nrt_light_envmap_rows: bad argument (0..65535 rows, bins >= 1, intensity[3])");
     return NRT_EINVAL;
   }
+  if (rows == 0) return NRT_OK;
+  if (!loc || !out) { set_error("nrt_light_envmap_rows: null argument"); return NRT_EINVAL; }
+  // the spectrum and falloff of nrt_light_create_point, in its operations
+  LightDev lt;
+  std::memset(&lt, 0, sizeof(lt));
+  lt.kind = 1;
+  float nrm = std::sqrt(inten[0] * inten[0] + inten[1] * inten[1] + inten[2] * inten[2]);
+  nrm = std::max(nrm, 1e-12f);
+  for (int i = 0; i < 3; ++i) lt.scaled_dir[i] = scale * (inten[i] / nrm);
+  lt.c = std::max(c, 1e-6f);
+  lt.l = std::max(lin, 1e-6f);
+  lt.q = std::max(q, 1e-6f);
+  k_light_envmap_rows<><<<dim3(ceil_div64(bins * bins, 64), (unsigned)rows), dim3(64), 0,
+                          (hipStream_t)stream>>>(lt, loc, bins, out);
+  return check_launch("k_light_envmap_rows");
+}
+
+}  // extern "C"
+
+// one launch of the fused sample kernel over P rays (persistent grid: every resident block slot;
+// independent blocks on a CU run out of phase, so one block's layer-boundary bubbles are filled
+// by the other's MFMAs)
+template <bool ROWS>
+static int launch_nerfle16(const ProgDev& pd, const float* rays, int64_t P, const float* ts, int S,
+                           const float* light, int64_t rays_per_light, int rows, int onehot,
+                           float* alpha, float* rgb_raw, hipStream_t st) {
+  auto kern = k_nerfle16<kNerfWaves, kNerfTiles, ROWS>;
+  const size_t lds = ring::KEngine<kNerfWaves, kNerfMaxF, kNerfDma>::lds_bytes(pd);
+  if (int rc = set_lds(kern, lds)) return rc;
+  const int blocks = resident_grid(kern, 64 * kNerfWaves, lds,
+                                   ceil_div64(P * (int64_t)S, 32 * kNerfTiles * kNerfWaves));
+  kern<<<dim3(blocks), dim3(64 * kNerfWaves), lds, st>>>(pd, rays, P, ts, S, light, rays_per_light,
+                                                         rows, onehot, alpha, rgb_raw);
+  return check_launch("k_nerfle16");
+}
+
+// nrt_nerfle_forward (rows = 1) and nrt_nerfle_forward_lights: light [rows, light_dim], ray p
+// under row p / rays_per_light
+static int nerfle_forward(const char* who, const nrt_mlp* first, const nrt_mlp* second,
+                          const float* rays, int64_t P, const float* ts, int32_t S,
+                          const float* light, int32_t light_dim, int64_t rows,
+                          int64_t rays_per_light, float* rgb, void* workspace, int precision,
+                          void* stream) {
+  const std::string w(who);
+  if (!first || !second || P < 0 || S < 1 || rows < 1) { set_error(w + ": bad argument"); return NRT_EINVAL; }
+  if (rows > 1 && (rays_per_light < 1 || P != rows * rays_per_light)) {
+    set_error(w + ": P must be rows * rays_per_light (one light row per camera)");
+    return NRT_EINVAL;
+  }
+  if (P == 0) return NRT_OK;
+  if (!rays || !ts || !light || !rgb || !workspace) { set_error(w + ": null argument"); return NRT_EINVAL; }
+  if (first->desc.in_size != 3 || first->desc.out != 65 || light_dim < 3 ||
+      second->desc.in_size != 67 + light_dim || second->desc.out != 3) {
+    set_error(w + ": expects first 3 -> 65 and second (67 + light_dim) -> 3 "
+                   "(nerf.py:162-172)");
+    return NRT_EINVAL;
+  }
+  if (rows > INT32_MAX / 4) { set_error(w + ": too many light rows"); return NRT_EUNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)P * S;
   char* ws = (char*)workspace;
   if (precision == NRT_FP16 && option(OPT_NERF_FUSED) != 0 &&
       nerf_fusable(first, second)) {
-    // NeRF+LE: the envmap (one constant per frame) is folded into the program; the host copy of
-    // it decides whether the cached program still holds (one small read-back per call)
+    // NeRF+LE: the envmap rows (constant per frame) are folded into the program, kNerfFoldRows
+    // rows (cameras) per program; the host copy of them decides whether the cached programs
+    // still hold (one small read-back per call, every row in one copy)
     std::vector<float> env;
     if (light_dim != 3) {
-      env.resize((size_t)light_dim);
+      env.resize((size_t)rows * light_dim);
       NRT_HIP(hipMemcpyAsync(env.data(), light, env.size() * 4, hipMemcpyDeviceToHost, st));
       NRT_HIP(hipStreamSynchronize(st));
     }
-    if (!second->nerf_prog || second->nerf_first_serial != first->serial ||
+    const int64_t groups = env.empty() ? 1 : ceil_div64(rows, kNerfFoldRows);
+    if (second->nerf_progs.empty() || second->nerf_first_serial != first->serial ||
         second->nerf_env != env) {
-      std::unique_ptr<nrt_prog> pr(new nrt_prog());
-      if (int rc = build_nerf_program(first, second, *pr, env.empty() ? nullptr : env.data()))
-        return rc;
-      second->nerf_prog = std::move(pr);
+      std::vector<std::unique_ptr<nrt_prog>> progs;
+      for (int64_t g = 0; g < groups; ++g) {
+        const int64_t r0 = g * kNerfFoldRows;
+        progs.emplace_back(new nrt_prog());
+        if (int rc = build_nerf_program(first, second, *progs.back(),
+                                        env.empty() ? nullptr : env.data() + r0 * light_dim,
+                                        (int)std::min<int64_t>(kNerfFoldRows, rows - r0)))
+          return rc;
+      }
+      second->nerf_progs = std::move(progs);
       second->nerf_first_serial = first->serial;
       second->nerf_env = env;
     }
-    const ProgDev& pd = second->nerf_prog->d;
-    if (!env.empty()) light = second->nerf_prog->unit_light;
     float* alpha = (float*)ws;
     float* rgb_raw = (float*)(ws + a256(n * 4));
-    auto kern = k_nerfle16<kNerfWaves, kNerfTiles>;
-    const size_t lds = ring::KEngine<kNerfWaves, kNerfMaxF, kNerfDma>::lds_bytes(pd);
-    if (int rc = set_lds(kern, lds)) return rc;
-    // persistent grid: every resident block slot (independent blocks on a CU run out of phase,
-    // so one block's layer-boundary bubbles are filled by the other's MFMAs)
-    const int blocks = resident_grid(kern, 64 * kNerfWaves, lds,
-                                     ceil_div64((int64_t)n, 32 * kNerfTiles * kNerfWaves));
     ProfScope prof("k_nerfle", st);
-    kern<<<dim3(blocks), dim3(64 * kNerfWaves), lds, st>>>(pd, rays, P, ts, S, light, alpha, rgb_raw);
-    if (int rc = check_launch("k_nerfle16")) return rc;
+    if (rows == 1) {
+      const nrt_prog& pr = *second->nerf_progs[0];
+      if (int rc = launch_nerfle16<false>(pr.d, rays, P, ts, S, env.empty() ? light : pr.unit_light,
+                                          0, 1, 0, alpha, rgb_raw, st))
+        return rc;
+    } else if (env.empty()) {
+      if (int rc = launch_nerfle16<true>(second->nerf_progs[0]->d, rays, P, ts, S, light,
+                                         rays_per_light, (int)rows, 0, alpha, rgb_raw, st))
+        return rc;
+    } else {
+      // groups of cameras, one folded program each (samples are ray-major: a group's rays, alpha
+      // and rgb_raw are one slice)
+      for (int64_t g = 0; g < groups; ++g) {
+        const int64_t r0 = g * kNerfFoldRows, p0 = r0 * rays_per_light;
+        const int rg = (int)std::min<int64_t>(kNerfFoldRows, rows - r0);
+        if (int rc = launch_nerfle16<true>(second->nerf_progs[g]->d, rays + p0 * 6,
+                                           rg * rays_per_light, ts, S, nullptr, rays_per_light, rg,
+                                           1, alpha + p0 * S, rgb_raw + p0 * S * 3, st))
+          return rc;
+      }
+    }
     k_nerf_composite_rm<><<<dim3(std::min<int64_t>(ceil_div64(P, 4), 16384)), dim3(256), 0, st>>>(
         alpha, rgb_raw, ts, P, S, rgb);
     return check_launch("k_nerf_composite_rm");
@@ -848,12 +975,30 @@ int nrt_nerfle_forward(const nrt_mlp* first, const nrt_mlp* second, const float*
   k_nerf_points<><<<dim3(blocks), dim3(256), 0, st>>>(rays, P, ts, S, pts);
   if (int rc = check_launch("k_nerf_points")) return rc;
   if (int rc = nrt_mlp_forward(first, pts, nullptr, (int64_t)n, f1, precision, stream)) return rc;
-  k_nerf_second_in<><<<dim3(blocks), dim3(256), 0, st>>>(f1, rays, P, S, light, light_dim, x2);
+  k_nerf_second_in<><<<dim3(blocks), dim3(256), 0, st>>>(f1, rays, P, S, light, light_dim,
+                                                          rows > 1 ? rays_per_light : 0, x2);
   if (int rc = check_launch("k_nerf_second_in")) return rc;
   if (int rc = nrt_mlp_forward(second, x2, nullptr, (int64_t)n, c2, precision, stream)) return rc;
   k_nerf_composite<><<<dim3(std::min<int64_t>(ceil_div64(P, 256), 4096)), dim3(256), 0, st>>>(
       f1, 65, c2, ts, P, S, rgb);
   return check_launch("k_nerf_composite");
+}
+
+extern "C" {
+
+int nrt_nerfle_forward(const nrt_mlp* first, const nrt_mlp* second, const float* rays, int64_t P,
+                       const float* ts, int32_t S, const float* light, int32_t light_dim,
+                       float* rgb, void* workspace, int precision, void* stream) {
+  return nerfle_forward("nrt_nerfle_forward", first, second, rays, P, ts, S, light, light_dim, 1,
+                        0, rgb, workspace, precision, stream);
+}
+
+int nrt_nerfle_forward_lights(const nrt_mlp* first, const nrt_mlp* second, const float* rays,
+                              int64_t P, const float* ts, int32_t S, const float* light,
+                              int32_t light_dim, int64_t rows, int64_t rays_per_light, float* rgb,
+                              void* workspace, int precision, void* stream) {
+  return nerfle_forward("nrt_nerfle_forward_lights", first, second, rays, P, ts, S, light,
+                        light_dim, rows, rays_per_light, rgb, workspace, precision, stream);
 }
 
 size_t nrt_plain_nerf_workspace_bytes(const nrt_mlp* first, const nrt_mlp* second, int64_t P,

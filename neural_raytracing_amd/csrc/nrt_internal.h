@@ -34,10 +34,12 @@ struct nrt_mlp {
   std::vector<float> host_bias;  // unfolded biases [layer][bias16_stride]
   std::vector<float> host_basis; // [in][F]
   std::vector<std::vector<float>> host_w;  // original weights per linear (init, hidden..., out)
-  // fused NeRFLE program built for (nerf_first, this) on first use (nrt_api_nerf.hip)
-  mutable std::unique_ptr<nrt_prog> nerf_prog;
+  // fused NeRFLE programs built for (nerf_first, this) on first use (nrt_api_nerf.hip): one, or
+  // with NeRF+LE and one light per camera one per group of folded envmap rows
+  mutable std::vector<std::unique_ptr<nrt_prog>> nerf_progs;
   mutable uint64_t nerf_first_serial = 0;
-  // NeRF+LE: the envmap the program's folded light column was built for (empty: point light)
+  // NeRF+LE: the envmap rows the programs' folded light columns were built for (empty: point
+  // light)
   mutable std::vector<float> nerf_env;
   uint64_t serial = 0;  // unique per created MLP (cache key; addresses can be reused)
   // nrt_mlp_refresh (nrt_refresh.hip): gather maps of the per-kernel fragment arrays, built on

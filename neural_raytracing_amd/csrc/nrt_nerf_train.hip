@@ -35,10 +35,11 @@ __global__ void k_nerf_split_first(const float* __restrict__ first_out, int O1, 
   }
 }
 
-// NeRFLE: columns 64.. of x2 = [r_d (3) | light (LK)]   (nerf.py:199-203)
+// NeRFLE: columns 64.. of x2 = [r_d (3) | light (LK)]   (nerf.py:199-203); light [rows, LK],
+// ray p reads row p / rpl (rpl = 0: one row for every ray)
 template <int = 0>
 __global__ void k_nerfle_tail_in(const float* __restrict__ rays, int64_t P, int64_t n,
-                                 const float* __restrict__ light, int LK,
+                                 const float* __restrict__ light, int LK, int64_t rpl,
                                  float* __restrict__ x2) {
   const int T = 3 + LK, in2 = 67 + LK;
   const int64_t ne = n * T;
@@ -47,7 +48,8 @@ __global__ void k_nerfle_tail_in(const float* __restrict__ rays, int64_t P, int6
     const int64_t i = e / T;
     const int c = (int)(e - i * T);
     const int64_t p = i % P;
-    x2[i * in2 + 64 + c] = c < 3 ? rays[p * 6 + 3 + c] : light[c - 3];
+    x2[i * in2 + 64 + c] =
+        c < 3 ? rays[p * 6 + 3 + c] : light[(rpl > 0 ? (p / rpl) * LK : 0) + c - 3];
   }
 }
 
@@ -311,11 +313,16 @@ int nrt_nerf_assemble(int32_t model, const float* first_out, const float* rays, 
   ProfScope prof("k_nerf_assemble", st);
   if (model == NRT_NERF_NERFLE) {
     const int in2 = 67 + extra_dim;
+    if (rays_per_latent > 0 && rays_per_latent < P && P % rays_per_latent != 0) {
+      set_error("nrt_nerf_assemble: P must be a multiple of rays_per_latent (rays per light row)");
+      return NRT_EINVAL;
+    }
     k_nerf_split_first<><<<dim3(grid_for(n * 65)), dim3(256), 0, st>>>(first_out, 65, n, nullptr,
                                                                          x2, in2, alpha_raw);
     if (int rc = check_launch("k_nerf_split_first")) return rc;
     k_nerfle_tail_in<><<<dim3(grid_for(n * (3 + extra_dim))), dim3(256), 0, st>>>(
-        rays, P, n, extra, extra_dim, x2);
+        rays, P, n, extra, extra_dim, rays_per_latent > 0 && rays_per_latent < P ? rays_per_latent : 0,
+        x2);
     return check_launch("k_nerfle_tail_in");
   }
   if (!lat2 || I < 0 || rays_per_latent < 1) {
@@ -417,7 +424,9 @@ int nrt_nerf_reduce(int32_t model, const float* d_first, const float* d_second, 
     set_error("nrt_nerf_reduce: null argument");
     return NRT_EINVAL;
   }
-  const int64_t rpl = model == NRT_NERF_PLAIN ? rays_per_latent : P;
+  // NERFLE: rays per light row; <= 0 or >= P is the one row every ray shares
+  const int64_t rpl = model == NRT_NERF_PLAIN || (rays_per_latent > 0 && rays_per_latent < P)
+                          ? rays_per_latent : P;
   if (rpl < 1 || P % rpl != 0) {
     set_error("nrt_nerf_reduce: P must be a multiple of rays_per_latent");
     return NRT_EINVAL;

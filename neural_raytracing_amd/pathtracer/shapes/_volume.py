@@ -12,7 +12,8 @@ from ..neural_blocks import (_check_versions, _forward_saving, _mlp_forward, _sa
 
 class VolumeSpec:
     """What one render needs besides tensors: the model selector, its two MLPs, how many rays
-    share a latent row (PlainNeRF: one camera's; NeRFLE: all) and the chunk bound in rays."""
+    share a row of ``extra`` (PlainNeRF's latent: one camera's; NeRFLE's light encoding: one
+    camera's with one light per camera, else all) and the chunk bound in rays."""
 
     def __init__(self, model, first, second, steps, rays_per_row, max_rays):
         self.model = model
@@ -83,7 +84,7 @@ def _add(total, part):
 class _VolumeFn(torch.autograd.Function):
     """rgb [P, 3] = volume render of rays [P, 6] with gradients for every nn.Linear weight and
     bias of both MLPs and for ``extra`` (PlainNeRF's latent [N, L]; NeRFLE's light encoding
-    [LK]).  Per sample it keeps first_out and rgb_raw (and what the MLPs' forwards save); the
+    [rows, LK], one row or one per camera).  Per sample it keeps first_out and rgb_raw (and what the MLPs' forwards save); the
     backward computes the points and the assembled inputs again."""
 
     @staticmethod
@@ -97,7 +98,7 @@ class _VolumeFn(torch.autograd.Function):
         with torch.no_grad():
             for r0, n, row0, rows, rpl in chunks(P, spec.rays_per_row, spec.max_rays):
                 r = rays[r0:r0 + n]
-                e = ex[row0:row0 + rows] if spec.plain else ex
+                e = ex[row0:row0 + rows]
                 nz = None if noise is None else noise[:, r0:r0 + n].contiguous()
                 pts, lat1 = _points(spec, r, ts, e, rpl)
                 first_out, save1 = _mlp(spec.first, h1, pts, lat1)
@@ -132,7 +133,7 @@ class _VolumeFn(torch.autograd.Function):
         g1 = g2 = None
         for r0, n, row0, rows, rpl, first_out, rgb_raw, save1, save2 in ctx.kept:
             r = rays[r0:r0 + n]
-            e = ex[row0:row0 + rows] if spec.plain else ex
+            e = ex[row0:row0 + rows]
             nz = None if ctx.noise is None else ctx.noise[:, r0:r0 + n].contiguous()
             # (each intermediate is dropped after its last reader: the MLP backwards' own
             # workspaces set the peak)
@@ -157,11 +158,11 @@ class _VolumeFn(torch.autograd.Function):
             del d_alpha
             part = None
             if want_extra:
-                part = torch.empty(rows, dim, device=dev) if spec.plain else torch.empty_like(ex)
+                part = torch.empty(rows, dim, device=dev)
             if want_extra and not spec.plain:
                 _lib.call("nrt_nerf_reduce", spec.model, None, _lib.ptr(d_second), n, S, dim,
                           spec.inter, rpl, _lib.ptr(part), _lib.ptr(ws), _lib.stream())
-                d_extra += part
+                d_extra[row0:row0 + rows] += part
             if not spec.plain:
                 d_second = None
             pts, lat1 = _points(spec, r, ts, e, rpl)
@@ -181,7 +182,10 @@ class _VolumeFn(torch.autograd.Function):
 
 def render_volume(spec, rays, ts, extra, noise=None):
     """``_VolumeFn`` on rays [P, 6], depths ts [S] and ``extra`` (latent [N, L] or light
-    encoding [LK]; float32 on the rays' device, its graph kept)."""
+    encoding [rows, LK], a plain [LK] being one row; float32 on the rays' device, its graph
+    kept)."""
+    if extra.dim() == 1:
+        extra = extra.reshape(1, -1)
     params = [t for m in (spec.first, spec.second) for lin in m._linears()
               for t in (lin.weight, lin.bias)]
     if any(t.device != rays.device for t in params):

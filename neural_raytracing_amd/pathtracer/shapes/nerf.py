@@ -12,7 +12,8 @@ import torch.nn as nn
 from ... import _lib
 from ..differentiable import needs_grad
 from ..neural_blocks import SkipConnMLP
-from ._volume import VolumeSpec, render_volume
+from .._handles import _host
+from ._volume import VolumeSpec, chunks, render_volume
 
 
 class PlainNeRF(nn.Module):
@@ -127,6 +128,31 @@ class NeRFLE(nn.Module):
         self.envmap = envmap
         self.steps = steps  # nerf.py:178 hard-codes 64; BASELINE cfg5 asks 256
 
+    def light_rows(self, lights, lead):
+        """Rows L of ``lights.location`` for rays of leading shape ``lead`` = [N, ...]: 1 (one
+        light for every camera) or N (camera n sees row n, nerf.py:193-197).  Decided from the
+        row count alone (equal rows and a single row are told apart by shape, not by value: no
+        host synchronisation).  Only the location varies per row: ``PointLights.envmap`` cannot
+        broadcast a per-row intensity against it."""
+        if getattr(self, "envmap", False) and not hasattr(lights, "envmap"):
+            raise _lib.NrtError("NeRFLE(envmap=True) needs PointLights (lights.envmap, "
+                                "lights.py:81-88)")
+        if getattr(lights, "location", None) is None:
+            raise _lib.NrtError("NeRFLE needs a light with a location (PointLights)")
+        L = lights.location.reshape(-1, 3).shape[0]
+        N = lead[0] if len(lead) > 1 else 1
+        if L != 1 and L != N:
+            raise _lib.NrtError(f"NeRFLE: {L} light locations for rays {tuple(lead)}: one "
+                                f"location, or one per camera ({N})")
+        inten = getattr(lights, "intensity", None)
+        if inten is not None and inten.dim() > 1 and inten.reshape(-1, inten.shape[-1]).shape[0] > 1:
+            i2 = inten.reshape(-1, inten.shape[-1])
+            if not bool((i2 == i2[:1]).all()):
+                raise _lib.NrtError("NeRFLE: one intensity for every light row (only the "
+                                    "location varies per camera; PointLights.envmap cannot "
+                                    "broadcast a per-row intensity)")
+        return L
+
     def forward(self, rays, lights):
         if not rays.is_cuda:
             raise _lib.NrtError("NeRFLE renders on the HIP path only: move it and the rays to the GPU")
@@ -134,57 +160,64 @@ class NeRFLE(nn.Module):
         flat = rays.reshape(-1, 6).float().contiguous()
         P = flat.shape[0]
         dev = flat.device
+        rows = self.light_rows(lights, lead)
+        # rays under one light row: one camera's, or every ray when one light serves them all
+        per = P // rows if rows > 1 else P
         # torch.linspace on the host: the same float32 sequence the CPU reference computes
         ts = torch.linspace(0, 2 + random.random() * 0.1, self.steps).to(dev)
+        envmap = getattr(self, "envmap", False)
         if needs_grad(self, lights):
-            if getattr(self, "envmap", False):
+            if envmap:
                 # nerf.py:183-191: the light's envmap at bins^2 directions (degree values passed
                 # as radians, as in the reference), differentiable in the light's parameters
-                if not hasattr(lights, "envmap"):
-                    raise _lib.NrtError("NeRFLE(envmap=True) needs PointLights (lights.envmap)")
+                # and its location; one encoding per location row
                 from ..utils import elev_azim_to_dir
                 points = torch.stack(torch.meshgrid(
                     torch.linspace(0, 180, self.bins, device=dev),
                     torch.linspace(0, 45, self.bins, device=dev), indexing="ij"),
                     dim=-1).reshape(-1, 2)
-                light = lights.envmap(elev_azim_to_dir(points)).reshape(-1).float()
+                light = lights.envmap(elev_azim_to_dir(points)).reshape(rows, -1).float()
             else:
-                light = lights.location.reshape(-1, 3)[0].detach().float().to(dev)
+                light = lights.location.reshape(-1, 3).detach().float().to(dev)
             if self.FUSED_TRAINING and P > 0:
-                spec = VolumeSpec(_lib.NRT_NERF_NERFLE, self.first, self.second, self.steps, P,
+                spec = VolumeSpec(_lib.NRT_NERF_NERFLE, self.first, self.second, self.steps, per,
                                   self.MAX_SAMPLES_PER_CALL // self.steps)
                 return render_volume(spec, flat, ts, light).reshape(lead + (3,))
             return self._forward_train(flat, ts, light).reshape(lead + (3,))
         lib = _lib.load(require_device=True)
-        if getattr(self, "envmap", False):
-            handle = getattr(lights, "nrt", None)
-            if handle is None or not hasattr(lights, "envmap"):
-                raise _lib.NrtError("NeRFLE(envmap=True) needs PointLights (lights.envmap, "
-                                    "lights.py:81-88)")
-            light = torch.empty(3 * self.bins * self.bins, device=dev)
-            _lib.call("nrt_light_envmap", handle(), self.bins, _lib.ptr(light), _lib.stream())
+        loc = lights.location.reshape(-1, 3).detach().float().to(dev).contiguous()
+        if envmap:
+            # every row's encoding in one launch, from the locations on the device
+            inten = _host(lights.intensity.reshape(-1, 3)[0])
+            light = torch.empty(rows, 3 * self.bins * self.bins, device=dev)
+            _lib.call("nrt_light_envmap_rows", _lib.ptr(loc), rows, inten.data_ptr(),
+                      float(lights.const), float(lights.linear), float(lights.square),
+                      float(lights.scale), self.bins, _lib.ptr(light), _lib.stream())
         else:
-            light = lights.location.reshape(-1, 3)[0].detach().float().to(dev).contiguous()
+            light = loc
+        dim = light.shape[1]
         rgb = torch.empty(P, 3, device=dev)
+        if P == 0:
+            return rgb.reshape(lead + (3,))
         first, second = self.first.nrt(), self.second.nrt()
         prec = _lib.precision_code()
-        per_ray = lib.nrt_nerfle_workspace_bytes_for(first, second, 1024, self.steps,
-                                                     light.numel(), prec) / 1024
-        chunk = max(1, min(P, int(self.MAX_WORKSPACE_BYTES // per_ray)))
-        ws = torch.empty(lib.nrt_nerfle_workspace_bytes_for(first, second, chunk, self.steps,
-                                                            light.numel(), prec),
+        per_ray = lib.nrt_nerfle_workspace_bytes_for(first, second, 1024, self.steps, dim,
+                                                     prec) / 1024
+        cmax = max(1, min(P, int(self.MAX_WORKSPACE_BYTES // per_ray)))
+        ws = torch.empty(lib.nrt_nerfle_workspace_bytes_for(first, second, cmax, self.steps, dim,
+                                                            prec),
                          dtype=torch.uint8, device=dev)
-        for r0 in range(0, P, chunk):
-            n = min(chunk, P - r0)
-            _lib.call("nrt_nerfle_forward", first, second, _lib.ptr(flat[r0:r0 + n]), n,
-                      _lib.ptr(ts), self.steps, _lib.ptr(light), light.numel(),
-                      _lib.ptr(rgb[r0:r0 + n]),
-                      _lib.ptr(ws), prec, _lib.stream())
+        # calls of whole cameras while one fits in the workspace bound, else pieces of one camera
+        for r0, n, row0, nrows, rpl in chunks(P, per, cmax):
+            _lib.call("nrt_nerfle_forward_lights", first, second, _lib.ptr(flat[r0:r0 + n]), n,
+                      _lib.ptr(ts), self.steps, _lib.ptr(light[row0:row0 + nrows]), dim, nrows,
+                      rpl, _lib.ptr(rgb[r0:r0 + n]), _lib.ptr(ws), prec, _lib.stream())
         return rgb.reshape(lead + (3,))
 
     def _forward_train(self, flat, ts, light):
-        """nerf.py:175-214 with autograd (point light or envmap encoding
-        ``light``): both MLPs on the HIP MLP kernels
+        """nerf.py:175-214 with autograd (``light`` [rows, dim] the point
+        light or envmap encoding, one row for every ray or one per camera, broadcast over the
+        camera axis as nerf.py:193-197 does): both MLPs on the HIP MLP kernels
         with nrt_mlp_backward behind them; the sample points and the rolled-cumprod compositing
         are tensor ops in the reference's order.  FP32 intermediates [S, P, 65 / 70]."""
         o, d = flat[:, :3], flat[:, 3:]
@@ -192,7 +225,13 @@ class NeRFLE(nn.Module):
         first = self.first(pts)
         latent = first[..., 1:]
         alpha = first[..., 0, None]
-        light_enc = light.reshape(1, 1, -1).expand(latent.shape[:-1] + (light.numel(),))
+        rows, dim = light.shape
+        P = flat.shape[0]
+        if rows == 1:
+            light_enc = light.reshape(1, 1, -1).expand(latent.shape[:-1] + (dim,))
+        else:
+            light_enc = light[:, None, :].expand(rows, P // rows, dim).reshape(1, P, dim) \
+                .expand(latent.shape[:-1] + (dim,))
         rgb = self.second(torch.cat([latent, d[None].expand(latent.shape[:-1] + (3,)), light_enc],
                                     dim=-1)).sigmoid()
         sigma = F.relu(alpha).squeeze(-1)
