@@ -104,13 +104,20 @@ static inline int set_lds(K kernel, size_t bytes) {
   return NRT_OK;
 }
 
+// LDS a ring launch leaves free: the compiler's resource report gives the ring kernels 256 bytes
+// of LDS of their own, which the runtime takes off the 160 KiB a launch may ask for
+// (hipFuncSetAttribute refused exactly 160 KiB of dynamic LDS for SphereSDF(348) + 8x256 F = 16
+// on the MI355X).  1 KiB is a deliberate margin, four times that figure: the figure is the
+// compiler's to change, and one constant serves every ring kernel without a query per launch.
+constexpr size_t kRingLdsReserve = 1024;
+
 // MarchArgs::stage (option "march_stage"): the per-wave line stages (LineStage) after the rest
-// of the block's LDS, when the launch queue is on and they fit in the CU's 160 KiB
+// of the block's LDS, when the launch queue is on and they fit in the CU's 160 KiB less the reserve
 static inline void stage_lds(MarchArgs& a, size_t& lds, int waves) {
   if (!a.queue || option(OPT_MARCH_STAGE) == 0) return;
   const size_t off = (lds + 15) & ~(size_t)15;
   const size_t need = off + (size_t)waves * kStageBytes;
-  if (off == 0 || need > 160 * 1024) return;
+  if (off == 0 || need + kRingLdsReserve > (size_t)kLdsBytes) return;
   a.stage = (int)off;
   lds = need;
 }
@@ -271,8 +278,10 @@ int ring16_launch(const nrt_sdf* s, Pass pass, const float* rays, int64_t P, con
                   const MarchOut& out, hipStream_t st);
 
 // ---- FP32 ring engine (nrt_ring_march32.hip) ----
-// SDF MLPs with a compiled FP32 ring kernel: hidden 128 / 256, F = 16 / 32 with 3 inputs and no
-// latent (ke = 48 / 80), <= 16 outputs, softplus or leaky_relu; any layer count and skip period.
+// SDF MLPs with a compiled FP32 ring kernel: hidden 128 / 256, 3 inputs and no latent with an
+// encoding of ke = 48 or 80 padded slots (F = 15 .. 22 or 31 .. 38; the scenes use 16 and 32),
+// <= 16 outputs, softplus or leaky_relu; any layer count and skip period; a bare MLP, or a
+// sphere blob whose table fits the block's LDS beside the ring (ring32_tables_fit).
 // Refreshed handles qualify (nrt_mlp_refresh re-gathers stream32).
 constexpr int kRing32Waves = 8;
 inline size_t ring32_sphere_bytes(const nrt_sdf* s) {
@@ -282,6 +291,15 @@ inline size_t ring32_sphere_bytes(const nrt_sdf* s) {
   const size_t pairs = (size_t)4 * ring32::sphere_pairs32(s->host_dev.n_spheres) * ring32::kPair32F4 * 16;
   return one > pairs ? one : pairs;
 }
+// the bias and sphere tables take at most 48 KiB, and ring | basis | biases | spheres
+// (Engine::lds_bytes) fits a block's LDS: beside the 128 KiB ring of a 256-wide MLP that is the
+// tighter bound (under 31 KiB of tables), and a launch past it fails instead of falling back.
+// kRingLdsReserve (above) stays free.
+inline bool ring32_tables_fit(const nrt_sdf* s, size_t ring_bytes) {
+  const size_t tables = ring32_sphere_bytes(s) + ring_bias_bytes(s);
+  return tables <= 48 * 1024 && ring_bytes + (size_t)s->mlp->host_dev.freqs * 16 + tables +
+                                        kRingLdsReserve <= (size_t)kLdsBytes;
+}
 inline bool ring32_supported(const nrt_sdf* s) {
   if (!s->mlp) return false;
   const MlpDev& m = s->mlp->host_dev;
@@ -289,7 +307,8 @@ inline bool ring32_supported(const nrt_sdf* s) {
   if (!((m.hidden == 128 || m.hidden == 256) && (m.ke == 48 || m.ke == 80) && m.in_size == 3 &&
         m.latent == 0 && m.out <= 16 && (act == NRT_ACT_SOFTPLUS || act == NRT_ACT_LEAKY_RELU)))
     return false;
-  return ring32_sphere_bytes(s) + ring_bias_bytes(s) <= 48 * 1024;
+  return ring32_tables_fit(s, m.hidden == 256 ? ring32::Engine<64, 20, kRing32Waves>::RING_BYTES
+                                              : ring32::Engine<32, 20, kRing32Waves>::RING_BYTES);
 }
 // call F.template operator()<KH, KE, ACT>() for the SDF's FP32 ring configuration
 template <class F>
@@ -321,6 +340,12 @@ constexpr int kRing3Waves = 8;
 inline bool ring3_supported(const nrt_sdf* s) {
   if (!s->mlp || (s->mlp->refreshed && !s->mlp->split_refreshed)) return false;
   const MlpDev& m = s->mlp->host_dev;
+  // (the tables ring32_supported admits fit beside the split ring too: at 256 it is the smaller
+  // ring, at 128 the 48 KiB cap leaves room beside its 96 KiB)
+  static_assert(ring3::Engine<8, 2, kRing3Waves>::RING_BYTES <= ring32::Engine<64, 20, kRing32Waves>::RING_BYTES &&
+                ring3::Engine<8, 3, kRing3Waves>::RING_BYTES <= ring32::Engine<64, 20, kRing32Waves>::RING_BYTES);
+  static_assert(ring3::Engine<4, 2, kRing3Waves>::RING_BYTES <= ring3::Engine<4, 3, kRing3Waves>::RING_BYTES &&
+                ring3::Engine<4, 3, kRing3Waves>::RING_BYTES + 38 * 16 + 48 * 1024 + kRingLdsReserve <= (size_t)kLdsBytes);
   return ring32_supported(s) && (m.ke3 == 64 || m.ke3 == 96);
 }
 // call F.template operator()<KH, KQ, ACT>() for the SDF's split ring configuration

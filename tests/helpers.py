@@ -1,4 +1,5 @@
 """Shared test helpers: build oracle and product objects from the same seed and copy weights."""
+import copy
 import random
 
 import torch
@@ -14,6 +15,16 @@ def copy_mlp(dst, src):
             a.weight.copy_(b.weight)
             a.bias.copy_(b.bias)
     return dst
+
+
+def double_copy(mod):
+    """float64 copy of an oracle module, plain tensor attributes (basis_p) included."""
+    m = copy.deepcopy(mod).double()
+    for sub in m.modules():
+        for k, v in list(vars(sub).items()):
+            if isinstance(v, torch.Tensor) and not isinstance(v, torch.nn.Parameter):
+                setattr(sub, k, v.double())
+    return m
 
 
 def product_mlp_like(src, activation):
@@ -93,12 +104,14 @@ class _Guarded:
         return bool((self.full[:GUARD] == want).all()) and bool((self.full[-GUARD:] == want).all())
 
 
-def intersect_poisoned(sh, rays, max_steps, precision, eps=5e-3, max_t=10.0, scan_max_t=2.2):
-    """nrt_sdf_intersect (primary) on a raw SDF handle with every output poisoned before the
-    launch (floats: the NaN POISON_F32, bytes: POISON_U8) and GUARD poisoned elements on both
-    sides of it, so that a store the march dropped cannot find the right bits left in recycled
-    memory and a store past an end is seen.  Returns ({t, hit, p, n, thr} on the host, the names
-    of the outputs whose guard bands changed)."""
+def intersect_poisoned(sh, rays, max_steps, precision, eps=5e-3, max_t=10.0, scan_max_t=2.2,
+                       primary=1):
+    """nrt_sdf_intersect on a raw SDF handle with every output poisoned before the launch
+    (floats: the NaN POISON_F32, bytes: POISON_U8) and GUARD poisoned elements on both sides of
+    it, so that a store the march dropped cannot find the right bits left in recycled memory and
+    a store past an end is seen.  `primary` = 1 runs the coarse scan too; with 0 nothing writes
+    thr, which stays poison.  Returns ({t, hit, p, n, raw, thr} on the host, the names of the
+    outputs whose guard bands changed)."""
     import ctypes
     from neural_raytracing_amd import _lib
     P, dev = rays.shape[0], rays.device
@@ -110,7 +123,7 @@ def intersect_poisoned(sh, rays, max_steps, precision, eps=5e-3, max_t=10.0, sca
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     lib = _lib.load(require_device=True)
     ws = torch.empty(max(lib.nrt_intersect_workspace_bytes(sh, P), 1), dtype=torch.uint8, device=dev)
-    mp = _lib.MarchParams(max_steps, eps, max_t, 1, scan_max_t, precision)
+    mp = _lib.MarchParams(max_steps, eps, max_t, primary, scan_max_t, precision)
     o = {k: v.out for k, v in g.items()}
     _lib.call("nrt_sdf_intersect", sh, _lib.ptr(rays), P, ctypes.byref(mp), _lib.ptr(o["t"]),
               _lib.ptr(o["hit"]), _lib.ptr(o["p"]), _lib.ptr(o["n"]), _lib.ptr(o["raw"]),
@@ -119,7 +132,7 @@ def intersect_poisoned(sh, rays, max_steps, precision, eps=5e-3, max_t=10.0, sca
     torch.cuda.synchronize()
     broken = [k for k, v in g.items() if not v.guards_intact()]
     out = {k: o[k].cpu() for k in ("t", "hit", "thr")}
-    out.update({k: o[k].cpu().reshape(P, 3) for k in ("p", "n")})
+    out.update({k: o[k].cpu().reshape(P, 3) for k in ("p", "n", "raw")})
     return out, broken
 
 

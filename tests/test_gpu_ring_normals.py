@@ -11,11 +11,10 @@ sdfs.py:184-197) after a ring32 / ring3 march.
   softplus / leaky_relu); ragged hit counts.  (The bare 8x256 MLP SDF runs through the same
   kernels in tests/test_gpu_configs.py and tests/test_gpu_split.py against the oracle.)
 """
-import copy
-
 import pytest
 import torch
 
+from tests.helpers import double_copy as _double
 from tests.helpers import lib_opt as _lib_opt
 from tests.report import report
 from tests.test_gpu_ring32 import _blob, _rays
@@ -57,15 +56,6 @@ def _run(sh, rays, code, ring):
     _lib.profile_enable(False)
     _lib_opt("normals_ring", 1)
     return (*out, counts)
-
-
-def _double(mod):
-    m = copy.deepcopy(mod).double()
-    for sub in m.modules():
-        for k, v in list(vars(sub).items()):
-            if isinstance(v, torch.Tensor) and not isinstance(v, torch.nn.Parameter):
-                setattr(sub, k, v.double())
-    return m
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp32-split"])

@@ -11,7 +11,6 @@ and three products per block, f32 accumulation.
   metric scene on a crop across the silhouette;
 * schedule invariance (persistent grid size) and ragged ray counts.
 """
-import copy
 import math
 import random
 
@@ -20,6 +19,7 @@ import torch
 
 import bench
 from oracle import pathtracer_ref as R
+from tests.helpers import double_copy as _double
 from tests.helpers import lib_opt as _lib_opt
 from tests.report import report
 from tests.test_gpu_configs import _agreement, _camera_rays, _mlp_sdf_pair
@@ -34,16 +34,6 @@ def _fp32():
     set_precision("fp32")
     yield
     set_precision("fp32")
-
-
-def _double(mod):
-    """float64 copy of an oracle module, plain tensor attributes (basis_p) included."""
-    m = copy.deepcopy(mod).double()
-    for sub in m.modules():
-        for k, v in list(vars(sub).items()):
-            if isinstance(v, torch.Tensor) and not isinstance(v, torch.nn.Parameter):
-                setattr(sub, k, v.double())
-    return m
 
 
 def _eval(mine, pts, prec, kernel):
