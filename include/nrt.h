@@ -481,6 +481,8 @@ int nrt_path_bounce_ex(const nrt_bsdf* bsdf, const nrt_light* light, const nrt_s
 #define NRT_CAM_NERF 0   /* NeRFCamera.sample_positions (cameras.py:23-54)                   */
 #define NRT_CAM_DTU 1    /* DTUCamera.sample_positions + lift (cameras.py:132-192)           */
 #define NRT_CAM_FOV 2    /* FoVPerspectiveCameras.sample_positions (renderer/cameras.py:539)  */
+#define NRT_CAM_NERFMM 3 /* NeRFMMCamera.sample_positions (cameras.py:70-99): nrt_raygen_mm,  */
+                         /* device parameters; not a kind of nrt_camera / nrt_raygen          */
 
 typedef struct {
   int32_t kind;
@@ -502,6 +504,34 @@ typedef struct {
 int nrt_raygen(const nrt_camera* host_cams, int32_t N, int32_t x0, int32_t y0, int32_t W,
                int32_t H, float with_noise, const float* noise, const float* positions,
                float* rays, void* stream);
+
+/* NeRFMMCamera (cameras.py:56-99, the NeRF-- camera: a translation, an axis-angle rotation and
+ * two focal lengths per camera, optimised with the field).  The parameters are DEVICE arrays
+ * t [N,3], angle [N], axis [N,3], focals [N,2] = (fx, fy): no parameter is read on the host and
+ * the calls allocate nothing.  The other arguments, the ray order rays[(n*W + x)*H + y][6] and
+ * the jitter (noise [2, W, H], u += (noise - 0.5) with_noise) are nrt_raygen's for NRT_CAM_NERF.
+ * Per ray, in float32 and the reference's order (cameras.py:85-98, rotate_vector utils.py:152-155;
+ * k = the camera's axis as given: the reference does not normalise it):
+ *   a = ((u - size/2) / fx, -((v - size/2) / fy), -1),  c = cos(angle), s = sin(angle)
+ *   r = a c + k (a.k) (1 - c) + (k x a) s,  r_d = r / max(|r|, 1e-12),  r_o = t */
+int nrt_raygen_mm(const float* t, const float* angle, const float* axis, const float* focals,
+                  int32_t N, int32_t size, int32_t x0, int32_t y0, int32_t W, int32_t H,
+                  float with_noise, const float* noise, const float* positions, float* rays,
+                  void* stream);
+/* Its backward: d_rays [N*W*H, 6] -> d_t [N,3], d_angle [N], d_axis [N,3], d_focals [N,2] (each
+ * overwritten; each may be NULL), what autograd gives through the statements above (nothing
+ * through a normalisation at its eps).  The 9 sums per camera over its W*H rays take two stages
+ * in a fixed order -- a thread's rays ascending, a wave by a fixed shuffle pattern, the waves of a
+ * block through LDS, the blocks of a camera (1024 rays each; none spans two cameras) in index
+ * order by a second kernel -- and no float atomics, so the same inputs give the same bits on
+ * every run.  workspace: nrt_raygen_mm_backward_workspace_bytes(N, W, H) device bytes. */
+size_t nrt_raygen_mm_backward_workspace_bytes(int32_t N, int32_t W, int32_t H);
+int nrt_raygen_mm_backward(const float* t, const float* angle, const float* axis,
+                           const float* focals, int32_t N, int32_t size, int32_t x0, int32_t y0,
+                           int32_t W, int32_t H, float with_noise, const float* noise,
+                           const float* positions, const float* d_rays, float* d_t,
+                           float* d_angle, float* d_axis, float* d_focals, void* workspace,
+                           void* stream);
 
 /* SurfaceInteraction.set_normals + to_local(-d) (interaction.py:73-78, sdfs.py:158-159):
  * frame[P,9] = coordinate_system(n) as [s | t | n] columns (row-major 3x3, may be NULL) and
@@ -691,6 +721,19 @@ int nrt_nerf_composite_backward(int32_t model, const float* alpha_raw, const flo
 int nrt_nerf_reduce(int32_t model, const float* d_first, const float* d_second, int64_t P,
                     int32_t S, int32_t dim, int32_t I, int64_t rays_per_latent, float* out,
                     void* workspace, void* stream);
+/* The rays' gradient (learnable cameras, e.g. nrt_raygen_mm_backward behind it): d_rays [P, 6]
+ * from d_pts [n, 3] (the first MLP's dx; pts = r_o + ts[s] r_d, nerf.py:51, :179) and d_second
+ * (the second MLP's dx, rows of second_stride floats).  One lane per ray, s ascending: a fixed
+ * order, no atomics.
+ *   d_rays[p, 0:3] = sum_s d_pts[i];  d_rays[p, 3:6] = sum_s ts[s] d_pts[i] + the direction term:
+ *   NERFLE  sum_s d_second[i, 64:67]  (r_d is columns 64..66 of x2, nerf.py:199-203;
+ *           second_stride = 67 + LK)
+ *   PLAIN   J^T sum_s d_second[i, 0:2]  (x2 = dir_to_elev_azim(r_d), utils.py:490-494, the same
+ *           for every sample of a ray; second_stride = 2): J through asin, atan2 and sqrt, zero
+ *           through a clamp that is active (as torch gives), then through the normalisation. */
+int nrt_nerf_rays_backward(int32_t model, const float* rays, int64_t P, const float* ts, int32_t S,
+                           const float* d_pts, const float* d_second, int32_t second_stride,
+                           float* d_rays, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Kernel timing (bench / profiling aid; no reference counterpart)

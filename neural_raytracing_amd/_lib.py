@@ -26,6 +26,7 @@ NRT_BSDF_NEURAL, NRT_BSDF_DIFFUSE, NRT_BSDF_CONDUCTOR = 0, 1, 2
 NRT_BSDF_PHONG, NRT_BSDF_PLASTIC = 3, 4
 NRT_BSDF_PARAMS = 12
 NRT_CAM_NERF, NRT_CAM_DTU, NRT_CAM_FOV = 0, 1, 2
+NRT_CAM_NERFMM = 3  # NeRFMMCamera: nrt_raygen_mm on device parameters (no nrt_camera struct)
 NRT_NERF_NERFLE, NRT_NERF_PLAIN = 0, 1
 
 
@@ -125,6 +126,11 @@ _SIGNATURES = {
     "nrt_shade_direct_learned_occ": (_I32, [_P, _P, _P, _P, _I32, _F, _P, _P, _P, _P, _P, _I64,
                                             _P, _P, _P, _P, _I32, _P]),
     "nrt_raygen": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "nrt_raygen_mm": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P,
+                             _P]),
+    "nrt_raygen_mm_backward_workspace_bytes": (ctypes.c_size_t, [_I32, _I32, _I32]),
+    "nrt_raygen_mm_backward": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P,
+                                      _P, _P, _P, _P, _P, _P, _P, _P]),
     "nrt_path_workspace_bytes": (ctypes.c_size_t, [_I64]),
     "nrt_path_bounce": (_I32, [_P, _P, _P, _I32, _P, _I32, _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                                _P, _P, _I32, _P]),
@@ -151,6 +157,7 @@ _SIGNATURES = {
     "nrt_nerf_composite_forward": (_I32, [_I32, _P, _P, _P, _I64, _I32, _P, _P]),
     "nrt_nerf_composite_backward": (_I32, [_I32, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
     "nrt_nerf_reduce": (_I32, [_I32, _P, _P, _I64, _I32, _I32, _I32, _I64, _P, _P, _P]),
+    "nrt_nerf_rays_backward": (_I32, [_I32, _P, _I64, _P, _I32, _P, _P, _I32, _P, _P]),
     "nrt_mlp_backward_workspace_bytes": (ctypes.c_size_t, [_P, _I64]),
     "nrt_mlp_backward": (_I32, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "nrt_mlp_backward_multi_workspace_bytes": (ctypes.c_size_t, [_P, _I32, _I64]),

@@ -1999,6 +1999,167 @@ __global__ void k_raygen(const nrt_camera* __restrict__ cams, int N, int x0, int
   rr[0] = o[0]; rr[1] = o[1]; rr[2] = o[2]; rr[3] = d[0]; rr[4] = d[1]; rr[5] = d[2];
 }
 
+// ------------------------------------------------------------------------------------------
+// NeRFMMCamera (cameras.py:56-99, the NeRF-- camera): the parameters are device arrays, read by
+// the kernels (t [N,3], angle [N], axis [N,3], focals [N,2]); nothing passes through the host.
+// ------------------------------------------------------------------------------------------
+// (u, v) of ray `pix` of a [W, H] tile: k_raygen's pixel convention and NRT_CAM_NERF's jitter
+__device__ __forceinline__ void mm_pixel_uv(int64_t pix, int xx, int yy, int x0, int y0, int W,
+                                            int H, float with_noise,
+                                            const float* __restrict__ noise,
+                                            const float* __restrict__ positions, float& u,
+                                            float& v) {
+  u = (float)(y0 + yy);
+  v = (float)(x0 + xx);
+  if (positions) { u = positions[pix * 2]; v = positions[pix * 2 + 1]; }
+  if (with_noise != 0.f && noise) {
+    u = u + (noise[pix] - 0.5f) * with_noise;
+    v = v + (noise[(int64_t)W * H + pix] - 0.5f) * with_noise;
+  }
+}
+
+// a = the camera-space direction (cameras.py:85-94) and r = rotate_vector(a, k, c, s)
+// (utils.py:152-155: a c + k (a.k) (1 - c) + (k x a) s, k used as given), in the reference's
+// float32 statement order
+__device__ __forceinline__ void mm_rotate(float u, float v, float half, float fx, float fy,
+                                          const float k[3], float c, float s, float a[3],
+                                          float r[3]) {
+  a[0] = (u - half) / fx;
+  a[1] = -((v - half) / fy);
+  a[2] = -1.f;
+  const float ak = (a[0] * k[0] + a[1] * k[1]) + a[2] * k[2];
+  const float x[3] = {k[1] * a[2] - k[2] * a[1], k[2] * a[0] - k[0] * a[2],
+                      k[0] * a[1] - k[1] * a[0]};
+  const float omc = 1.f - c;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) r[j] = (a[j] * c + (k[j] * ak) * omc) + x[j] * s;
+}
+
+// One thread, one ray; rays[(n*W + x)*H + y][6] as k_raygen.
+template <int = 0>
+__global__ void k_raygen_mm(const float* __restrict__ t, const float* __restrict__ angle,
+                            const float* __restrict__ axis, const float* __restrict__ focals,
+                            int N, int size, int x0, int y0, int W, int H, float with_noise,
+                            const float* __restrict__ noise, const float* __restrict__ positions,
+                            float* __restrict__ rays) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)N * W * H;
+  if (i >= total) return;
+  const int yy = (int)(i % H);
+  const int xx = (int)((i / H) % W);
+  const int n = (int)(i / ((int64_t)W * H));
+  float u, v;
+  mm_pixel_uv((int64_t)xx * H + yy, xx, yy, x0, y0, W, H, with_noise, noise, positions, u, v);
+  const float k[3] = {axis[n * 3], axis[n * 3 + 1], axis[n * 3 + 2]};
+  const float ang = angle[n];
+  float a[3], r[3];
+  mm_rotate(u, v, (float)((double)size * 0.5), focals[n * 2], focals[n * 2 + 1], k, cosf(ang),
+            sinf(ang), a, r);
+  normalize3(r[0], r[1], r[2], 1e-12f);
+  float* rr = rays + i * 6;
+  rr[0] = t[n * 3]; rr[1] = t[n * 3 + 1]; rr[2] = t[n * 3 + 2];
+  rr[3] = r[0]; rr[4] = r[1]; rr[5] = r[2];
+}
+
+// Backward of k_raygen_mm, stage 1.  Per ray the 9 gradient terms (g_t [3], g_angle, g_k [3],
+// g_fx, g_fy), summed per camera in a fixed order and without atomics: block (b, n) owns rays
+// [b * kMMSlice, (b + 1) * kMMSlice) of camera n (a block never spans two cameras); a thread adds
+// its rays in ascending order, a wave sums its 64 lanes by a fixed xor-shuffle butterfly, the
+// block its 4 waves through LDS in wave order.  partial[(n * gridDim.x + b) * 9 + c].
+constexpr int kMMThreads = 256;
+constexpr int kMMSlice = 1024;  // rays of one camera per first-stage block
+constexpr int kMMCols = 9;
+
+template <int = 0>
+__global__ void __launch_bounds__(kMMThreads)
+k_raygen_mm_bwd_partial(const float* __restrict__ angle, const float* __restrict__ axis,
+                        const float* __restrict__ focals, int size, int x0, int y0, int W, int H,
+                        float with_noise, const float* __restrict__ noise,
+                        const float* __restrict__ positions, const float* __restrict__ d_rays,
+                        float* __restrict__ partial) {
+  __shared__ float sm[kMMThreads / 64][kMMCols];
+  const int n = blockIdx.y;
+  const int64_t m = (int64_t)W * H;
+  const int64_t j0 = (int64_t)blockIdx.x * kMMSlice;
+  const int64_t j1 = j0 + kMMSlice < m ? j0 + kMMSlice : m;
+  const float k[3] = {axis[n * 3], axis[n * 3 + 1], axis[n * 3 + 2]};
+  const float ang = angle[n];
+  const float c = cosf(ang), s = sinf(ang), omc = 1.f - c;
+  const float fx = focals[n * 2], fy = focals[n * 2 + 1];
+  const float half = (float)((double)size * 0.5);
+  float acc[kMMCols];
+#pragma unroll
+  for (int q = 0; q < kMMCols; ++q) acc[q] = 0.f;
+  for (int64_t j = j0 + threadIdx.x; j < j1; j += kMMThreads) {
+    const int yy = (int)(j % H), xx = (int)(j / H);
+    float u, v;
+    mm_pixel_uv(j, xx, yy, x0, y0, W, H, with_noise, noise, positions, u, v);
+    float a[3], r[3];
+    mm_rotate(u, v, half, fx, fy, k, c, s, a, r);
+    const float* dr = d_rays + ((int64_t)n * m + j) * 6;
+    const float g[3] = {dr[3], dr[4], dr[5]};
+    const float len = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    float gr[3] = {0.f, 0.f, 0.f};
+    if (len >= 1e-12f) {  // F.normalize: r / max(|r|, eps); below eps the gradient is dropped
+      const float d[3] = {r[0] / len, r[1] / len, r[2] / len};
+      const float dg = (d[0] * g[0] + d[1] * g[1]) + d[2] * g[2];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) gr[q] = (g[q] - d[q] * dg) / len;
+    }
+    const float ak = (a[0] * k[0] + a[1] * k[1]) + a[2] * k[2];
+    const float kg = (k[0] * gr[0] + k[1] * gr[1]) + k[2] * gr[2];
+    const float ag = (a[0] * gr[0] + a[1] * gr[1]) + a[2] * gr[2];
+    // g x k, k x a, a x g
+    const float gxk[3] = {gr[1] * k[2] - gr[2] * k[1], gr[2] * k[0] - gr[0] * k[2],
+                          gr[0] * k[1] - gr[1] * k[0]};
+    const float kxa[3] = {k[1] * a[2] - k[2] * a[1], k[2] * a[0] - k[0] * a[2],
+                          k[0] * a[1] - k[1] * a[0]};
+    const float axg[3] = {a[1] * gr[2] - a[2] * gr[1], a[2] * gr[0] - a[0] * gr[2],
+                          a[0] * gr[1] - a[1] * gr[0]};
+    const float ga0 = (c * gr[0] + (k[0] * kg) * omc) + s * gxk[0];
+    const float ga1 = (c * gr[1] + (k[1] * kg) * omc) + s * gxk[1];
+    const float g_c = ag - ak * kg;
+    const float g_s = (kxa[0] * gr[0] + kxa[1] * gr[1]) + kxa[2] * gr[2];
+    acc[0] += dr[0]; acc[1] += dr[1]; acc[2] += dr[2];
+    acc[3] += c * g_s - s * g_c;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) acc[4 + q] += omc * (ak * gr[q] + kg * a[q]) + s * axg[q];
+    acc[7] += -(a[0] / fx) * ga0;
+    acc[8] += -(a[1] / fy) * ga1;
+  }
+#pragma unroll
+  for (int q = 0; q < kMMCols; ++q)
+    for (int o = 32; o >= 1; o >>= 1) acc[q] += __shfl_xor(acc[q], o);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < kMMCols; ++q) sm[wave][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < kMMCols) {
+    float tsum = sm[0][threadIdx.x];
+    for (int w = 1; w < kMMThreads / 64; ++w) tsum += sm[w][threadIdx.x];
+    partial[((int64_t)n * gridDim.x + blockIdx.x) * kMMCols + threadIdx.x] = tsum;
+  }
+}
+
+// Stage 2: element (n, c) adds its camera's nb partials in block-index order and writes the
+// output it belongs to (each may be null).
+template <int = 0>
+__global__ void k_raygen_mm_bwd_final(const float* __restrict__ partial, int nb, int N,
+                                      float* __restrict__ d_t, float* __restrict__ d_angle,
+                                      float* __restrict__ d_axis, float* __restrict__ d_focals) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N * kMMCols) return;
+  const int n = e / kMMCols, c = e - n * kMMCols;
+  float tsum = 0.f;
+  for (int b = 0; b < nb; ++b) tsum += partial[((int64_t)n * nb + b) * kMMCols + c];
+  if (c < 3) { if (d_t) d_t[n * 3 + c] = tsum; }
+  else if (c == 3) { if (d_angle) d_angle[n] = tsum; }
+  else if (c < 7) { if (d_axis) d_axis[n * 3 + c - 4] = tsum; }
+  else if (d_focals) d_focals[n * 2 + c - 7] = tsum;
+}
+
 template <int = 0>
 __global__ void k_composite(const float* __restrict__ rgb, const float* __restrict__ thr,
                             const uint8_t* __restrict__ hit, int N, int W, int H, int alpha,

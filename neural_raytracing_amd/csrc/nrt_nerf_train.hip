@@ -251,6 +251,77 @@ __global__ void k_nerf_reduce_final(const float* __restrict__ partial, int nb, i
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// the rays' gradient (learnable cameras): pts = r_o + ts[s] r_d (nerf.py:51, :179) and the second
+// MLP's view of r_d.  One lane per ray, s ascending: a fixed order, no atomics.
+//   d_rays[p, 0:3] = sum_s d_pts[i],  d_rays[p, 3:6] = sum_s ts[s] d_pts[i] + direction term
+// NERFLE: r_d is columns 64..66 of x2 (nerf.py:199-203): the term is sum_s d_second[i, 64:67].
+// PLAIN: x2 = dir_to_elev_azim(r_d) (utils.py:490-494) is the same for every sample of a ray, so
+// the two columns of d_second are summed first and the Jacobian applied once: through asin /
+// atan2 / sqrt, the clamps (no gradient where one is active, as torch gives) and F.normalize.
+// ------------------------------------------------------------------------------------------
+template <bool PLAIN>
+__global__ void k_nerf_rays_backward(const float* __restrict__ rays, int64_t P,
+                                     const float* __restrict__ ts, int S,
+                                     const float* __restrict__ d_pts,
+                                     const float* __restrict__ d_second, int sstride,
+                                     float* __restrict__ d_rays) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < P;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    float go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < S; ++s) {
+      const int64_t i = (int64_t)s * P + p;
+      const float t = ts[s];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float g = d_pts[i * 3 + k];
+        go[k] += g;
+        gd[k] += t * g;
+      }
+      if constexpr (PLAIN) {
+        gs[0] += d_second[i * sstride];
+        gs[1] += d_second[i * sstride + 1];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gs[k] += d_second[i * sstride + 64 + k];
+      }
+    }
+    if constexpr (PLAIN) {
+      // dir_elev_azim's statements (nrt_kernels.h) again, then their gradient
+      const float vx = rays[p * 6 + 3], vy = rays[p * 6 + 4], vz = rays[p * 6 + 5];
+      const float len = sqrtf(vx * vx + vy * vy + vz * vz);
+      const float nrm = fmaxf(len, 1e-12f);
+      const float nx = vx / nrm, ny = vy / nrm, nz = vz / nrm;
+      const float lo = -1.f + 1e-7f, hi = 1.f - 1e-7f;
+      const float x = fminf(fmaxf(nx, lo), hi), z = fminf(fmaxf(nz, lo), hi);
+      const float w = (1.f - x * x) - z * z;
+      const float q = sqrtf(fmaxf(w, 1e-10f));
+      const float den = x * x + q * q;
+      // elev = asin(z); azim = atan2(x, q): d/dx = q / den, d/dq = -x / den
+      const float gq = w >= 1e-10f ? (-x / den) * gs[1] / (2.f * q) : 0.f;  // dL/dw
+      float gx = (q / den) * gs[1] + gq * (-2.f * x);
+      float gz = gs[0] / sqrtf(1.f - z * z) + gq * (-2.f * z);
+      if (nx < lo || nx > hi) gx = 0.f;
+      if (nz < lo || nz > hi) gz = 0.f;
+      // back through n = v / max(|v|, eps): (g - n (n . g)) / |v|, g = (gx, 0, gz)
+      if (len >= 1e-12f) {
+        const float ng = nx * gx + nz * gz;
+        gs[0] = (gx - nx * ng) / len;
+        gs[1] = (0.f - ny * ng) / len;
+        gs[2] = (gz - nz * ng) / len;
+      } else {
+        gs[0] = gx / nrm; gs[1] = 0.f; gs[2] = gz / nrm;
+      }
+    }
+    float* o = d_rays + p * 6;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      o[k] = go[k];
+      o[3 + k] = gd[k] + gs[k];
+    }
+  }
+}
+
 static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int grid_for(int64_t elems) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((elems + 255) / 256, 8192));
@@ -405,6 +476,31 @@ int nrt_nerf_composite_backward(int32_t model, const float* alpha_raw, const flo
     k_nerf_vol_backward<false><<<grid, dim3(64), 0, st>>>(alpha_raw, rgb_raw, ts, P, S, d_out, cpw,
                                                           d_alpha_raw, d_rgb_raw);
   return check_launch("k_nerf_vol_backward");
+}
+
+int nrt_nerf_rays_backward(int32_t model, const float* rays, int64_t P, const float* ts, int32_t S,
+                           const float* d_pts, const float* d_second, int32_t second_stride,
+                           float* d_rays, void* stream) {
+  if (P < 0 || S < 1 || (model != NRT_NERF_NERFLE && model != NRT_NERF_PLAIN) ||
+      second_stride < (model == NRT_NERF_NERFLE ? 67 : 2)) {
+    set_error("nrt_nerf_rays_backward: bad argument");
+    return NRT_EINVAL;
+  }
+  if (P == 0) return NRT_OK;
+  if (!rays || !ts || !d_pts || !d_second || !d_rays) {
+    set_error("nrt_nerf_rays_backward: null argument");
+    return NRT_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)std::min<int64_t>(ceil_div64(P, 64), 65536));
+  ProfScope prof("k_nerf_rays_backward", st);
+  if (model == NRT_NERF_PLAIN)
+    k_nerf_rays_backward<true><<<grid, dim3(64), 0, st>>>(rays, P, ts, S, d_pts, d_second,
+                                                          second_stride, d_rays);
+  else
+    k_nerf_rays_backward<false><<<grid, dim3(64), 0, st>>>(rays, P, ts, S, d_pts, d_second,
+                                                           second_stride, d_rays);
+  return check_launch("k_nerf_rays_backward");
 }
 
 int nrt_nerf_reduce(int32_t model, const float* d_first, const float* d_second, int64_t P,

@@ -87,6 +87,97 @@ class NeRFCamera(Camera):
         return self.rays_tile(0, 0, W, H, size, with_noise, positions=pos)
 
 
+class _RaygenMMFn(torch.autograd.Function):
+    """rays [N*W*H, 6] of a NeRFMMCamera tile (``nrt_raygen_mm``) with the gradients of t, angle,
+    axis and focals from ``nrt_raygen_mm_backward``; the parameters stay on the device."""
+
+    @staticmethod
+    def forward(ctx, t, angle, axis, focals, geom, noise, positions):
+        ctx.geom, ctx.noise, ctx.positions = geom, noise, positions
+        ctx.save_for_backward(t, angle, axis, focals)
+        return _raygen_mm(t, angle, axis, focals, geom, noise, positions)
+
+    @staticmethod
+    def backward(ctx, d_rays):
+        if torch.is_grad_enabled():
+            raise _lib.NrtError("second derivatives through NeRFMMCamera's rays are not on the "
+                                "HIP path")
+        lib = _lib.load(require_device=True)
+        t, angle, axis, focals = ctx.saved_tensors
+        size, x0, y0, W, H, with_noise = ctx.geom
+        N, dev = t.shape[0], t.device
+        d_rays = d_rays.detach().float().reshape(-1, 6).contiguous()
+        outs = [torch.empty_like(p) if need else None
+                for p, need in zip((t, angle, axis, focals), ctx.needs_input_grad[:4])]
+        ws = torch.empty(lib.nrt_raygen_mm_backward_workspace_bytes(N, W, H), dtype=torch.uint8,
+                         device=dev)
+        _lib.call("nrt_raygen_mm_backward", _lib.ptr(t), _lib.ptr(angle), _lib.ptr(axis),
+                  _lib.ptr(focals), N, size, x0, y0, W, H, with_noise, _lib.ptr(ctx.noise),
+                  _lib.ptr(ctx.positions), _lib.ptr(d_rays), *[_lib.ptr(o) for o in outs],
+                  _lib.ptr(ws), _lib.stream())
+        return (*outs, None, None, None)
+
+
+def _raygen_mm(t, angle, axis, focals, geom, noise, positions):
+    size, x0, y0, W, H, with_noise = geom
+    N = t.shape[0]
+    rays = torch.empty(N * W * H, 6, device=t.device)
+    _lib.call("nrt_raygen_mm", _lib.ptr(t), _lib.ptr(angle), _lib.ptr(axis), _lib.ptr(focals), N,
+              size, x0, y0, W, H, with_noise, _lib.ptr(noise), _lib.ptr(positions),
+              _lib.ptr(rays), _lib.stream())
+    return rays
+
+
+@dataclass
+class NeRFMMCamera(Camera):
+    """The NeRF-- camera (cameras.py:56-99): per camera a translation ``t`` [N, 3], a rotation by
+    ``angle`` [N] or [N, 1] about ``axis`` [N, 3] (used as given: the reference does not normalise
+    it) and two focal lengths ``focals`` [N, 2], all learnable.  Rays come from ``nrt_raygen_mm``,
+    which reads the parameters on the device; when one of them takes a gradient the rays carry
+    ``nrt_raygen_mm_backward`` behind them."""
+    t: torch.Tensor = None
+    angle: torch.Tensor = None
+    axis: torch.Tensor = None
+    focals: torch.Tensor = None
+    device: str = "cuda"
+
+    def __len__(self):
+        return self.t.shape[0]
+
+    def parameters(self):
+        # (the reference's body names undefined variables, cameras.py:68: its evident meaning)
+        return [self.angle, self.axis, self.t, self.focals]
+
+    def rays_tile(self, x0, y0, W, H, size, with_noise=False, positions=None):
+        """[N, W, H, 1, 6] rays for tile rows x0.. and cols y0.. (u = col, v = row)."""
+        N = len(self)
+        ps = (self.t, self.angle, self.axis, self.focals)
+        if not all(p.is_cuda for p in ps):
+            raise _lib.NrtError("NeRFMMCamera makes its rays on the HIP path only: move t, angle, "
+                                "axis and focals to the GPU")
+        dev = self.t.device
+        noise = None
+        if with_noise:
+            # two rand_like draws in the reference (u then v): [2, W, H]
+            noise = torch.rand(2, W, H, device=dev)
+        t, angle, axis, focals = (p.float().reshape(N, k).contiguous()
+                                  for p, k in zip(ps, (3, 1, 3, 2)))
+        if positions is not None:
+            positions = positions.detach().float().contiguous()
+        geom = (int(size), int(x0), int(y0), int(W), int(H), float(with_noise or 0.0))
+        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
+            rays = _RaygenMMFn.apply(t, angle, axis, focals, geom, noise, positions)
+        else:
+            rays = _raygen_mm(t, angle, axis, focals, geom, noise, positions)
+        return rays.reshape(N, W, H, 1, 6)
+
+    def sample_positions(self, position_samples, sampler, bundle_size=4, size=512,
+                         with_noise=False, N=1):
+        W, H, _ = position_samples.shape
+        pos = position_samples.float().contiguous()
+        return self.rays_tile(0, 0, W, H, size, with_noise, positions=pos)
+
+
 def _f32(v, device="cpu"):
     t = v if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float32)
     return t.to(device=device, dtype=torch.float32).reshape(-1)

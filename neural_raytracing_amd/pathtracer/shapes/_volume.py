@@ -83,9 +83,11 @@ def _add(total, part):
 
 class _VolumeFn(torch.autograd.Function):
     """rgb [P, 3] = volume render of rays [P, 6] with gradients for every nn.Linear weight and
-    bias of both MLPs and for ``extra`` (PlainNeRF's latent [N, L]; NeRFLE's light encoding
-    [rows, LK], one row or one per camera).  Per sample it keeps first_out and rgb_raw (and what the MLPs' forwards save); the
-    backward computes the points and the assembled inputs again."""
+    bias of both MLPs, for ``extra`` (PlainNeRF's latent [N, L]; NeRFLE's light encoding
+    [rows, LK], one row or one per camera) and for the rays (learnable cameras: both MLPs' dx
+    into ``nrt_nerf_rays_backward``; asked for only when the rays take a gradient).  Per sample
+    it keeps first_out and rgb_raw (and what the MLPs' forwards save); the backward computes the
+    points and the assembled inputs again."""
 
     @staticmethod
     def forward(ctx, spec, rays, ts, extra, noise, *params):
@@ -128,7 +130,8 @@ class _VolumeFn(torch.autograd.Function):
         S, dev = spec.steps, rays.device
         dim = ex.shape[-1]
         d_out = d_out.detach().float().reshape(-1, 3).contiguous()
-        want_extra = ctx.needs_input_grad[3]
+        want_extra, want_rays = ctx.needs_input_grad[3], ctx.needs_input_grad[1]
+        d_rays = torch.empty_like(rays) if want_rays else None
         d_extra = torch.zeros_like(ex) if want_extra else None
         g1 = g2 = None
         for r0, n, row0, rows, rpl, first_out, rgb_raw, save1, save2 in ctx.kept:
@@ -148,8 +151,9 @@ class _VolumeFn(torch.autograd.Function):
             del alpha_raw
             # NeRFLE's first MLP reads the second's dx, PlainNeRF's its dlatent
             dx2, dlat2, gr2 = mlp_first_order(spec.second, h2, save2, x2, lat2, d_rgb,
-                                              not spec.plain, spec.plain)
+                                              not spec.plain or want_rays, spec.plain)
             d_second = dlat2 if spec.plain else dx2
+            d_dir = dx2 if want_rays else None  # the second MLP's dx: the rays' direction term
             del x2, lat2, d_rgb, dx2, dlat2
             d_first_out = torch.empty_like(first_out)
             _lib.call("nrt_nerf_assemble_backward", spec.model, _lib.ptr(d_alpha),
@@ -166,9 +170,14 @@ class _VolumeFn(torch.autograd.Function):
             if not spec.plain:
                 d_second = None
             pts, lat1 = _points(spec, r, ts, e, rpl)
-            _, dlat1, gr1 = mlp_first_order(spec.first, h1, save1, pts, lat1, d_first_out,
-                                            False, spec.plain and want_extra)
+            d_pts, dlat1, gr1 = mlp_first_order(spec.first, h1, save1, pts, lat1, d_first_out,
+                                                want_rays, spec.plain and want_extra)
             del pts, lat1, d_first_out
+            if want_rays:
+                _lib.call("nrt_nerf_rays_backward", spec.model, _lib.ptr(r), n, _lib.ptr(ts), S,
+                          _lib.ptr(d_pts), _lib.ptr(d_dir), d_dir.shape[1],
+                          _lib.ptr(d_rays[r0:r0 + n]), _lib.stream())
+            del d_pts, d_dir
             if want_extra and spec.plain:
                 _lib.call("nrt_nerf_reduce", spec.model, _lib.ptr(dlat1), _lib.ptr(d_second), n, S,
                           dim, spec.inter, rpl, _lib.ptr(part), _lib.ptr(ws), _lib.stream())
@@ -177,7 +186,7 @@ class _VolumeFn(torch.autograd.Function):
         if g1 is None:  # no rays
             g1 = [None] * (2 * len(spec.first._linears()))
             g2 = [None] * (2 * len(spec.second._linears()))
-        return (None, None, None, d_extra, None, *g1, *g2)
+        return (None, d_rays, None, d_extra, None, *g1, *g2)
 
 
 def render_volume(spec, rays, ts, extra, noise=None):
@@ -191,7 +200,4 @@ def render_volume(spec, rays, ts, extra, noise=None):
     if any(t.device != rays.device for t in params):
         raise _lib.NrtError("the NeRF's parameters and the rays are on different devices: move "
                             "the module to the GPU (.to(device)) to train it")
-    if rays.requires_grad:
-        raise _lib.NrtError("the fused volume render has no gradient for the rays: detach them "
-                            "(camera poses are not trained on this path)")
     return _VolumeFn.apply(spec, rays, ts, extra.contiguous(), noise, *params)

@@ -24,8 +24,8 @@ class PlainNeRF(nn.Module):
     draws ``random.random()`` for ``ts = linspace(0.4, 2 + r*0.1, steps)`` and the density noise
     ``randn * 1e-3`` per sample (nerf.py:50, :66; on the device, ``noise=`` injects it) and
     returns ``(rgb + 1) / 2`` with the reference's compositing.  ``lights`` is unused, as there.
-    When a parameter or the latent takes a gradient the same render runs as one autograd
-    Function (``_volume._VolumeFn``) in chunks of the same bound.
+    When a parameter, the latent or the rays (a learnable camera) take a gradient the same
+    render runs as one autograd Function (``_volume._VolumeFn``) in chunks of the same bound.
     """
 
     MAX_SAMPLES_PER_CALL = 1 << 22
@@ -51,7 +51,8 @@ class PlainNeRF(nn.Module):
         if not rays.is_cuda:
             raise _lib.NrtError("PlainNeRF renders on the HIP path only: move it and the rays to "
                                 "the GPU")
-        train = needs_grad(self) or (torch.is_grad_enabled() and self.latent.requires_grad)
+        train = needs_grad(self) or (torch.is_grad_enabled() and
+                                     (self.latent.requires_grad or rays.requires_grad))
         lead = rays.shape[:-1]
         if len(lead) < 2 or lead[0] != self.latent.shape[0]:
             raise _lib.NrtError(f"PlainNeRF: rays {tuple(rays.shape)} must be [N, ..., 6] with "
@@ -166,7 +167,8 @@ class NeRFLE(nn.Module):
         # torch.linspace on the host: the same float32 sequence the CPU reference computes
         ts = torch.linspace(0, 2 + random.random() * 0.1, self.steps).to(dev)
         envmap = getattr(self, "envmap", False)
-        if needs_grad(self, lights):
+        if needs_grad(self, lights) or (torch.is_grad_enabled() and rays.requires_grad):
+            # (rays that take a gradient: a learnable camera, also with a frozen network)
             if envmap:
                 # nerf.py:183-191: the light's envmap at bins^2 directions (degree values passed
                 # as radians, as in the reference), differentiable in the light's parameters
